@@ -22,6 +22,16 @@ strong scaling, value = 1 volume per step / max-over-ranks step time.  --replica
 every rank a full volume of its own capture (weak scaling).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--cutoff 5.7] [--lines 3.0] [--band 8] [--replicas]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what takes
+runs of its own: the exact in-support evaluation count of the frozen workload (`compute`, one
+nlosgr_count_support pass) and the CPU baselines (`cpu_baseline`, `cpu_baseline_c1`; `--no-cpu-baseline`
+leaves them out of a full run).  `--dump-outputs DIR` writes what the last timed step handed its caller
+as DIR/<name>.npy (float32): the training step's loss, the six updated parameter tensors and Adam's first
+moments (0.1 x the step's gradients, the snapshot's moments being zero), or the forward-only
+configs' histogram.  Inputs are seeded, so two builds can be compared array for array; more than 60 MB
+in all is cut down to a fixed, seeded sample of each array's rows.
 
 Launch: under a launcher (torch.distributed.run: WORLD_SIZE set) every process is one rank and
 WORLD_SIZE must equal --gpus.  Without one, `--gpus N` > 1 starts N fresh child interpreters of this
@@ -219,6 +229,25 @@ class Snapshot:
         tr.adam.step_count, tr.iteration = self.count, self.iteration
 
 
+DUMP_BUDGET = 60 * 2 ** 20     # bytes of .npy payload per run (--dump-outputs)
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET):
+    """Write {name: tensor} as path/<name>.npy (float32).  When the arrays exceed `budget` bytes in all,
+    every array keeps the same fraction of its rows (dim 0): a sorted sample drawn from a generator
+    seeded with 0, so the same rows are written run after run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    g = torch.Generator().manual_seed(0)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if total > budget and t.dim() > 0 and t.shape[0] > 1:
+            keep = max(1, t.shape[0] * budget // total)
+            t = t[torch.randperm(t.shape[0], generator=g)[:keep].sort().values.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def _sync(dev):
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
@@ -312,17 +341,22 @@ def stub_main(a, world, rank):
     x = torch.randn(256, 256, generator=torch.Generator().manual_seed(rank))
     grad = torch.zeros(64)
 
+    last = {}
+
     def step():
         t0 = time.perf_counter()
         y = x @ x
         grad.fill_(float(y[0, 0]))
         if world > 1:
             dist.all_reduce(grad)
+        last["y"] = y
         ms = (time.perf_counter() - t0) * 1e3
         return lambda: (ms, 0.0)
 
     elapsed, own, phases = timed_run(step, a.steps, a.warmup, world, dev)
     ranks = _gather_ranks(world, rank, own, phases, "cpu")
+    if rank == 0 and a.dump_outputs and last:
+        dump_outputs(a.dump_outputs, {"grad": grad, "y": last["y"]})
     if rank == 0:
         print(json.dumps({"metric": "stub (launcher rehearsal)", "value": world * 1000.0 * a.steps / (elapsed * 1e3),
                           "unit": "steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -360,7 +394,12 @@ def main():
                     help="Mahalanobis support radius; 5.7 = parity grade (SURVEY §8d), <= 0 = dense")
     ap.add_argument("--lines", default="",
                     help="comma-separated extra cutoffs timed the same way (reported under 'lines'); '' = none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the support count (compute.evaluations) and the "
+                         "CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; see the module docstring)")
     ap.add_argument("--preset", default="cuda", choices=("cuda", "torch"),
                     help="convention preset: cuda = the reference's CUDA path, torch = its torch path (SURVEY A.3)")
     ap.add_argument("--mode", default="noocl", choices=("noocl", "netf", "occl"),
@@ -403,7 +442,7 @@ def main():
     from nlosgr.distributed import wall_rows
     from nlosgr.model import features_flat
     from nlosgr.render import count_support, render_forward
-    from nlosgr.train import TrainStep
+    from nlosgr.train import GROUPS, TrainStep
     from nlosgr.volume import Scene, make_config
 
     ng, H, W, T, ns, fwd_only = CONFIGS[a.config]
@@ -437,6 +476,7 @@ def main():
                               nwall_total=H * W if (sharded or a.band > 1) else H * W * world,
                               events={"fwd": ev_fwd, "bwd": ev_bwd})
             snap = Snapshot(train)
+            last = {}       # what the newest step returned (device tensors; read only by --dump-outputs)
 
             def step():
                 snap.restore()
@@ -444,20 +484,31 @@ def main():
                     params = [model._mu.detach(), model._scaling.detach(), model._rotation.detach(),
                               model._opacity.detach(), features_flat(model).detach().contiguous()]
                     ev_fwd[0].record(stream)
-                    render_forward(*params, geo, cfg, True, False)
+                    last["hist"] = render_forward(*params, geo, cfg, True, False)[0]
                     ev_fwd[1].record(stream)
                     return lambda: (ev_fwd[0].elapsed_time(ev_fwd[1]), 0.0)
-                train()
+                last["loss"] = train()
                 return train.phase_ms   # HIP events of the step's phases (occl: summed over its batches)
 
             elapsed, own, evs = timed_run(step, a.steps, a.warmup, world, dev)
             fwd_ms = [e[0] for e in evs]
             bwd_ms = [e[1] for e in evs] if not fwd_only else []
+            if a.dump_outputs and rank == 0 and cut == a.cutoff and last:
+                # before the snapshot comes back: the model and the moments are the last step's
+                tag = f"_band{b0}of{b1}" if a.band > 1 else ""
+                if fwd_only:
+                    arrays = {"hist" + tag: last["hist"]}
+                else:
+                    arrays = {"loss" + tag: last["loss"]}
+                    arrays.update({n + tag: t for n, t in zip(GROUPS, train._tensors)})
+                    arrays.update({f"adam_m_{n}{tag}": t for n, t in zip(GROUPS, train.adam.exp_avg)})
+                dump_outputs(a.dump_outputs, arrays, DUMP_BUDGET // len(bands))
+            last.clear()
             snap.restore()
             params = [model._mu.detach(), model._scaling.detach(), model._rotation.detach(),
                       model._opacity.detach(), features_flat(model).detach().contiguous()]
-            if a.selection == "aabb":
-                pairs = rays = evals = None      # no support count for the box filter
+            if not a.full or a.selection == "aabb":
+                pairs = rays = evals = None      # plain run: not counted; no support count for the box filter
             else:   # occl: the same (pair, ray, bin) support as noocl at this cutoff
                 pairs, rays, evals = count_support(*params, geo, replace(cfg, mode="noocl") if a.mode == "occl" else cfg)
             per_band.append({"band": [b0, b1], "ms_per_step": elapsed * 1000.0 / a.steps,
@@ -551,7 +602,7 @@ def main():
                       "evaluations": b["evaluations"]})
     if lines:
         out["lines"] = lines
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(a.config, a.cutoff, preset=a.preset, mode=a.mode)
         except Exception as e:  # report, never fake

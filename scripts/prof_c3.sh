@@ -16,7 +16,7 @@ pass() {   # name, rocprofv3 options...
 }
 for ps in $PASSES; do
   case $ps in
-    bench) timeout -k 10 600 python bench.py $ARGS > $O/bench_default.log 2> $O/bench_default.err; rc=$?
+    bench) timeout -k 10 600 python bench.py --full $ARGS > $O/bench_default.log 2> $O/bench_default.err; rc=$?
            tail -1 $O/bench_default.log | cut -c1-400; [ $rc -eq 0 ] || { tail -5 $O/bench_default.err; exit $rc; } ;;
     kt) pass kt --kernel-trace --stats || exit $? ;;
     fetch) pass fetch --pmc FETCH_SIZE || exit $? ;;

@@ -6,7 +6,7 @@ set -o pipefail
 O=gpurun_out/lines_r05; mkdir -p $O
 run() {   # name, timeout, bench args...
   local n=$1 t=$2; shift 2
-  NLOSGR_BENCH_PROGRESS=1 timeout -k 10 $t python bench.py "$@" > $O/$n.json 2> $O/$n.err || { tail -3 $O/$n.err; return 1; }
+  NLOSGR_BENCH_PROGRESS=1 timeout -k 10 $t python bench.py --full "$@" > $O/$n.json 2> $O/$n.err || { tail -3 $O/$n.err; return 1; }
   tail -1 $O/$n.json | cut -c1-240
 }
 run c3_netf 400 --mode netf --steps 5 --warmup 2 --no-cpu-baseline || exit 1

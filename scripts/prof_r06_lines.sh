@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 run() {   # name, timeout, bench args...  (under rocprofv3 --kernel-trace --stats: kernel stats beside the line)
   local n=$1 t=$2; shift 2
   rm -rf /tmp/kt_$n
-  NLOSGR_BENCH_PROGRESS=1 timeout -k 10 $t rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$n -o prof -- python3 bench.py "$@" > $O/$n.json 2> $O/$n.err || { tail -3 $O/$n.err; return 1; }
+  NLOSGR_BENCH_PROGRESS=1 timeout -k 10 $t rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$n -o prof -- python3 bench.py --full "$@" > $O/$n.json 2> $O/$n.err || { tail -3 $O/$n.err; return 1; }
   cp $(find /tmp/kt_$n -name "*kernel_stats.csv" | head -1) $O/${n}_kernel_stats.csv
   tail -1 $O/$n.json | cut -c1-240
 }
