@@ -21,6 +21,9 @@
  *   nlosgr_bboxes       <- compute_gaussian_bboxes_kernel include/bbox_compute.cuh:76-120,
  *                          GaussianModel.get_bboxes gaussian_model/gaussian_model.py:140-178
  *   nlosgr_carve_votes  <- the voting loop of space_carving gaussian_model/gaussian_utils.py:88-99
+ *   nlosgr_voxelize     <- evaluation() -> gaussian2volume main.py:374-387, nlos_helpers.py:40-69, with the
+ *                          two sums of estimate_rho_w_no_occlusion(out_separately=True)
+ *                          gaussian_model/gaussian_model.py:346-364 on a regular voxel grid
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -38,7 +41,7 @@
 extern "C" {
 #endif
 
-#define NLOSGR_ABI_VERSION 8
+#define NLOSGR_ABI_VERSION 9
 
 /* convention presets */
 enum {
@@ -291,6 +294,49 @@ NLOSGR_API int nlosgr_adam(const nlosgr_adam_group* groups, int32_t ngroups, lon
  * ------------------------------------------------------------------------------------- */
 NLOSGR_API int nlosgr_carve_votes(const float* coords, long long nvox, const float* walls, const float* radius,
                        int32_t nwall, int32_t* votes, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Reconstruction output (ABI 9): the trained Gaussians on a regular voxel grid, and maximum
+ * projections of such a volume.  The reference's evaluation() calls gaussian2volume (main.py:374-387,
+ * nlos_helpers.py:40-69), which evaluates estimate_rho_w(out_separately=True) at the spherical
+ * samples of the central wall point; its per-sample "density" there is a flattened [Ng * Na]
+ * per-Gaussian tensor, so the quantities implemented here are the two sums of
+ * estimate_rho_w_no_occlusion(out_separately=True) (gaussian_model.py:346-364) at voxel centre x:
+ *     density(x)        = sum_g sigma_g pdf_g(x)                  (gaussian_model.py:357)
+ *     albedo_density(x) = sum_g sigma_g rho_g(cam) pdf_g(x)       (gaussian_model.py:359)
+ * sigma_g = sigmoid(opacity_g), rho_g(cam) = max(0, 0.5 + SH_g(dir(mu_g - cam))) (:350-355), pdf_g under
+ * the preset / scaling_modifier / sh_degree of `g` exactly as in nlosgr_render_fwd, zero where the
+ * Mahalanobis distance m^2 > cutoff^2 when opt->cutoff > 0 (dense when <= 0).
+ * Each voxel's sum is formed in ascending Gaussian-index order without atomics: the outputs are
+ * bitwise repeatable and do not depend on how the grid is cut into bricks (a sub-grid with the same
+ * table values gives the same numbers).
+ * ------------------------------------------------------------------------------------- */
+typedef struct nlosgr_voxel_grid {
+    int32_t nx, ny, nz;       /* extents, each in 1..1024 */
+    const float* xs;          /* [nx] device table of voxel-centre x coordinates: uniform, ascending (the */
+    const float* ys;          /* [ny]  caller's linspace; the kernels read the coordinates from the tables, */
+    const float* zs;          /* [nz]  like nlosgr_geometry.r) */
+} nlosgr_voxel_grid;          /* voxel (ix, iy, iz) is stored at (ix*ny + iy)*nz + iz: meshgrid('ij') order,
+                                 as in space_carving (gaussian_utils.py:91-93) */
+
+/* Scratch bytes for nlosgr_voxelize (host only; 0 with a message in nlosgr_last_error on invalid input).
+ * Uses opt->cutoff only; a non-zero mode, selection or ray_cache is invalid. */
+NLOSGR_API size_t nlosgr_voxel_workspace_bytes(const nlosgr_gaussians* g, const nlosgr_voxel_grid* grid,
+                                    const nlosgr_options* opt);
+
+/* density_out / albedo_out [nx,ny,nz] (either may be NULL), overwritten.  cam: DEVICE [3], the position the
+ * SH albedo is viewed from (the reference uses the central wall point).  With ng == 0 the outputs are
+ * zero-filled.  In culled mode a Gaussian whose cutoff box is not finite (NaN / inf parameters) is skipped,
+ * as the forward skips it. */
+NLOSGR_API int nlosgr_voxelize(const nlosgr_gaussians* g, const nlosgr_voxel_grid* grid, const float* cam,
+                    const nlosgr_options* opt, void* workspace, float* density_out, float* albedo_out,
+                    void* hip_stream);
+
+/* Maximum of vol [nx,ny,nz] along `axis` (0..2) and the index of that maximum (ties: lowest index, so an
+ * all-zero column gives (0, 0)); max_out (float) / argmax_out (int32), either may be NULL, are laid out as
+ * the two remaining axes in their original order. */
+NLOSGR_API int nlosgr_volume_project(const float* vol, int32_t nx, int32_t ny, int32_t nz, int32_t axis,
+                          float* max_out, int32_t* argmax_out, void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

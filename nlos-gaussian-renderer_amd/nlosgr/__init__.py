@@ -12,6 +12,7 @@ Layers:
     nlosgr.train           fused training iteration (nlosgr_mse + render fwd/bwd + nlosgr_adam)
     nlosgr.data            Zaragoza capture format, data_shuffle, whole-volume targets / geometry
     nlosgr.checkpoint      reference-keyed checkpoints loadable with weights_only=True
+    nlosgr.voxelize        reconstruction output: Gaussians -> voxel grid, max projections, depth map
 """
 from . import _lib  # noqa: F401
 from .geometry import Geometry, build_geometry, relay_wall_grid, volume_box_point  # noqa: F401

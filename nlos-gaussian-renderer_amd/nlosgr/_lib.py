@@ -52,6 +52,11 @@ class Rays(ctypes.Structure):
                 ("t", _P), ("cam", _P)]
 
 
+class VoxelGrid(ctypes.Structure):
+    _fields_ = [("nx", ctypes.c_int32), ("ny", ctypes.c_int32), ("nz", ctypes.c_int32), ("xs", _P), ("ys", _P),
+                ("zs", _P)]
+
+
 class AdamGroup(ctypes.Structure):
     _fields_ = [("param", _P), ("grad", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("n", ctypes.c_longlong),
                 ("lr", ctypes.c_double)]
@@ -59,7 +64,7 @@ class AdamGroup(ctypes.Structure):
 
 ADAM_MAX_GROUPS = 8  # NLOSGR_ADAM_MAX_GROUPS
 MAX_PER_RAY = 256   # NLOSGR_MAX_PER_RAY
-ABI_VERSION = 8     # NLOSGR_ABI_VERSION
+ABI_VERSION = 9     # NLOSGR_ABI_VERSION
 
 # nlosgr_options.flags variant selection (NLOSGR_FLAG_*; A/B timing and parity cross-checks, 0 in production)
 FLAG_FLOAT_DRAIN = 0x100   # forward: fp32 claim drain instead of the fixed-point drain
@@ -75,7 +80,8 @@ FLAG_TILE_NOBIN = 0x8000   # ray-tile engine: in-kernel cull instead of the tile
 EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "nlosgr_count_support", "nlosgr_fx_info",
            "nlosgr_bboxes", "nlosgr_rays_workspace_bytes", "nlosgr_filter_rays", "nlosgr_rays_fwd",
            "nlosgr_rays_bwd", "nlosgr_rays_analytic", "nlosgr_mse_workspace_bytes", "nlosgr_mse", "nlosgr_adam",
-           "nlosgr_carve_votes", "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
+           "nlosgr_carve_votes", "nlosgr_voxel_workspace_bytes", "nlosgr_voxelize", "nlosgr_volume_project",
+           "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
 _load_error = None
@@ -122,6 +128,13 @@ def load():
     lib.nlosgr_adam.restype = ctypes.c_int
     lib.nlosgr_carve_votes.argtypes = [_P, ctypes.c_longlong, _P, _P, ctypes.c_int32, _P, _P]
     lib.nlosgr_carve_votes.restype = ctypes.c_int
+    PVG = ctypes.POINTER(VoxelGrid)
+    lib.nlosgr_voxel_workspace_bytes.argtypes = [PG, PVG, POPT]
+    lib.nlosgr_voxel_workspace_bytes.restype = ctypes.c_size_t
+    lib.nlosgr_voxelize.argtypes = [PG, PVG, _P, POPT, _P, _P, _P, _P]
+    lib.nlosgr_voxelize.restype = ctypes.c_int
+    lib.nlosgr_volume_project.argtypes = [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]
+    lib.nlosgr_volume_project.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

@@ -9,6 +9,8 @@ HIP kernels (no dense [Ng, Na] torch tensors).
                                                                         x Y^2 on both outputs)
     compute_loss                           nlos_helpers.py:280-346     (same loss / equal_loss; no per-step .mat
                                                                         dump unless args.save_loss_mat is set)
+    gaussian2volume                        nlos_helpers.py:40-69       (same signature; 'voxel' returns the regular-grid
+                                                                        volumes and projection maps, 'mesh' raises)
 Without args.use_cuda_renderer the default path T conventions apply (preset "torch"); args.occlusion
 selects the 'netf' self-transmittance model like gaussian_model.py:297-325.  args.render_cutoff
 (optional, default 0 = dense, the reference's exact semantics) enables support culling at that
@@ -170,3 +172,31 @@ def compute_loss(args, model, data_kwargs, optim_kwargs, device=None):
         import scipy.io
         scipy.io.savemat("./loss_compare.mat", {"nlos": target.cpu().numpy(), "pred": pred.detach().cpu().numpy()})
     return loss, equal_loss
+
+
+def gaussian2volume(args, model, data_kwargs, camera_pos, resolution=128, mode='voxel'):
+    """nlos_helpers.py:40-69 with the reference's signature.  mode 'voxel' (an empty name in the reference)
+    returns {'density', 'albedo' [R,R,R], 'front', 'depth' [R,R], 'front_density', 'depth_density', 'grid'}:
+    the no-occlusion sums of estimate_rho_w_no_occlusion(out_separately=True) (gaussian_model.py:346-364) on
+    a resolution^3 grid over the hidden volume, the albedo volume's maximum projection along the wall
+    normal y with its depth map, and the same two maps of the density volume (nlosgr.voxelize).  The SH
+    albedo is viewed from camera_pos (the reference passes the central wall point, main.py:378-382).
+    Conventions follow the rendering path as in gaussian_transient_rendering; args.render_cutoff
+    (default 0 = dense, the reference's semantics) sets the support cutoff.  mode 'mesh' is the
+    reference's open3d Poisson reconstruction (:50-69), which needs open3d: it raises."""
+    if mode.lower() == 'mesh':
+        raise NotImplementedError("nlosgr: gaussian2volume(mode='mesh') needs open3d (absent); use mode='voxel'")
+    if mode.lower() != 'voxel':
+        raise ValueError(f"nlosgr: unknown gaussian2volume mode {mode!r}")
+    from .voxelize import VoxelGrid, front_view, voxelize
+    preset = "cuda" if getattr(args, "use_cuda_renderer", False) and CUDA_RENDERER is not None else "torch"
+    pos = [float(v) for v in data_kwargs["volume_position"]]
+    grid = VoxelGrid(pos, float(data_kwargs["volume_size"]), int(resolution))
+    cam = torch.as_tensor(camera_pos, dtype=torch.float32, device=model._mu.device).reshape(3)
+    dens, alb = voxelize(model, grid, cam, preset=preset, cutoff=float(getattr(args, "render_cutoff", 0.0) or 0.0),
+                         scaling_modifier=float(getattr(args, "scaling_modifier", 1.0)),
+                         sh_degree=int(model.active_sh_degree))
+    front, depth = front_view(alb, grid)
+    front_d, depth_d = front_view(dens, grid)
+    return {"density": dens, "albedo": alb, "front": front, "depth": depth, "front_density": front_d,
+            "depth_density": depth_d, "grid": grid}
