@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define NLOSGR_ABI_VERSION 9
+#define NLOSGR_ABI_VERSION 10
 
 /* convention presets */
 enum {
@@ -150,6 +150,10 @@ typedef struct {
                                            kernel instead of reading the tile bins (A/B: same selections) */
 #define NLOSGR_FLAG_FX_MAXUNIT   0x4000 /* forward FX drain: unit from the largest amplitude bound (the round-5
                                            rule, diagnostics: shows the precision the quantile unit recovers) */
+#define NLOSGR_FLAG_FX_NOTWIN    0x10000 /* forward no-occlusion FX drain: one ray per lane (the single-segment
+                                            drain) instead of two adjacent rays of a pair per lane (A/B, tests) */
+#define NLOSGR_FLAG_FX_TWIN_STATS 0x20000 /* forward twin drain: also record the longest twin (bins) in
+                                             nlosgr_fx_info (one global atomic per twin: diagnostics, slow) */
 
 /* Scratch bytes needed by fwd/bwd for this problem (caller allocates, 256-B aligned); includes
  * nwall*ng*24 B for the ray cache when opt->ray_cache is set (OCCL mode: the row cache,
@@ -191,10 +195,12 @@ NLOSGR_API int nlosgr_count_support(const nlosgr_gaussians* g, const nlosgr_geom
                          void* hip_stream);
 
 /* Fixed-point forward state after an nlosgr_render_fwd on `workspace` (same g / geo / opt): info_out
- * (DEVICE, [4] int32, overwritten, copied on the stream) = {E: the unit 2^-E of the fixed-point drain,
+ * (DEVICE, [8] int32, overwritten, copied on the stream) = {E: the unit 2^-E of the fixed-point drain,
  * E of the launch's largest amplitude bound, LDS histogram flushes into the u64 row, bright segments
- * (peak >= 2^24 units, added straight into the u64 row)}; all zero when the forward did not take the
- * fixed-point drain.  Diagnostics / tests. */
+ * (peak >= 2^24 units, added straight into the u64 row), bright Gaussians, twins (two adjacent rays of a
+ * pair drained by one lane as one segment), twins split at the merge guard (drained as two segments), the
+ * longest twin in bins (NLOSGR_FLAG_FX_TWIN_STATS only)};
+ * all zero when the forward did not take the fixed-point drain.  Diagnostics / tests.  (ABI 10: [8], was [4].) */
 NLOSGR_API int nlosgr_fx_info(const nlosgr_gaussians* g, const nlosgr_geometry* geo, const nlosgr_options* opt,
                    const void* workspace, int32_t* info_out, void* hip_stream);
 

@@ -78,7 +78,9 @@ struct KArgs {
     int accum;                   // backward batches after the first add into the partial slabs
     unsigned long long* hfx;     // forward FX drain: fixed-point histogram [P][nr] (u64, integer adds)
     int* fx_info;                // forward FX drain: [0] unit exponent E (fx_unit_kernel), [1] E of the launch's
-                                 // largest bound, [2] LDS flushes, [3] bright segments, [4] bright Gaussians
+                                 // largest bound, [2] LDS flushes, [3] bright segments, [4] bright Gaussians,
+                                 // [5] twins drained as one segment, [6] twins split (fx_twin_setup), [7] the
+                                 // longest twin in bins (NLOSGR_FLAG_FX_TWIN_STATS)
     const float* fx_bound;       // forward FX drain: amplitude bound per Gaussian [ng] (fx_bound_kernel)
     const int* fx_blist;         // forward FX drain: the bright Gaussians (fx_blist_kernel), [fx_info[4]]
 };
@@ -268,6 +270,9 @@ constexpr int kRQ = 256;
 __device__ __forceinline__ unsigned pack_ray(int slot, int i, int j) {
     return (unsigned)slot | ((unsigned)i << 8) | ((unsigned)j << 20);
 }
+// twin entries (the no-occlusion FX forward, see fx_twin_setup): slots are lanes (< 64), so bit 7 of the slot
+// byte marks an entry that stands for the two adjacent cells (i, j) and (i, j + 1) of one pair
+constexpr unsigned kTwinBit = 0x80u;
 
 // ------------------------------------------------------------------------------------------
 // forward
@@ -286,12 +291,20 @@ constexpr int kSteps = NLOSGR_FSTEPS;     // bins per lane per drain round (the 
 #define NLOSGR_FSTEPS_NETF 20
 #endif
 constexpr int kStepsNetf = NLOSGR_FSTEPS_NETF;
-static_assert(kStepsNetf <= kSteps && kStepsNetf % 2 == 0, "the layouts' pads hold kSteps bins");
+// the twin drain (fx_twin_setup) runs longer rounds: a round costs two sets of exp2 seeds, and its unions are
+// longer than single segments (one GPU, 24 / 28 / 32 bins: fwd 657.6 / 642.2 / 632.5 ms; another, 32 / 36 / 40 /
+// 48 bins: 635.7 / 625.1 / 623.7 / 623.6 ms)
+#ifndef NLOSGR_FSTEPS_TWIN
+#define NLOSGR_FSTEPS_TWIN 36
+#endif
+constexpr int kStepsTwin = NLOSGR_FSTEPS_TWIN;
+constexpr int kStepsPad = kSteps > kStepsTwin ? kSteps : kStepsTwin;   // the layouts' pads hold the longest round
+static_assert(kStepsNetf <= kSteps && kStepsNetf % 2 == 0 && kStepsTwin % 2 == 0, "the layouts' pads hold kStepsPad bins");
 // round 6: 28-bin rounds (with the refill deal at 56 idle lanes and 2 placement claim rounds) for the
 // no-occlusion and bin-integrated forwards: C3 734.8 -> 714.4 ms, C4 binint 1150 -> 1090 ms; netf measured
 // 883.7 -> 893.8 ms at 28 and keeps 20
-template <int MODE>
-__device__ __forceinline__ constexpr int fsteps() { return MODE == NLOSGR_MODE_NETF ? kStepsNetf : kSteps; }
+template <int MODE, bool TW = false>
+__device__ __forceinline__ constexpr int fsteps() { return TW ? kStepsTwin : (MODE == NLOSGR_MODE_NETF ? kStepsNetf : kSteps); }
 #ifndef NLOSGR_REFILL
 #define NLOSGR_REFILL 48
 #endif
@@ -308,18 +321,14 @@ constexpr int kBRefill = NLOSGR_BREFILL;   // backward: same rule
 #ifndef NLOSGR_FXPERM
 #define NLOSGR_FXPERM 1   // FX refill permutation (the deal, see fx_perm): with the bank placement 745.7 vs 750.6 ms
 #endif
-#ifndef NLOSGR_FXBAL
-#define NLOSGR_FXBAL 0    // with NLOSGR_FXPERM: residue balance at refill instead of the placement (fx_balance, opt-in)
-#endif
 struct FwdLayout {
     int hist, owner, rayq, wave_stride, total;  // offsets in floats
     // fx: the fixed-point drain needs no claim table and no per-lane pad bins (22.7 KB per C3
     // workgroup instead of 26.6 KB: 7 workgroups per CU)
     __host__ __device__ FwdLayout(int nr, int nt, int np_, bool fx = false) {
         const int off = al4(2 * (nt + np_));  // float2 theta table [nt], float2 phi table [np]
-        hist = 0;                             // [nr + kSteps] bins + [kSteps + 64] pad bins (fx: [nr + kSteps + 2])
-        // fx: the histogram's fields, then 16 residue counters of the refill balance (fx_balance)
-        owner = fx ? al4(nr + kSteps + 4) + (NLOSGR_FXPERM && NLOSGR_FXBAL ? 16 : 0) : al4(nr + 2 * kSteps + 64);   // u8 [nr] claim table
+        hist = 0;                             // [nr + kStepsPad] bins + [kStepsPad + 64] pad bins (fx: [nr + kStepsPad + 2])
+        owner = fx ? al4(nr + kStepsPad + 4) : al4(nr + 2 * kStepsPad + 64);   // u8 [nr] claim table
         rayq = owner + (fx ? 0 : al4((nr + 3) / 4));   // uint [kRQ] ring
         wave_stride = al4(rayq + kRQ);
         hist += off; owner += off; rayq += off;
@@ -332,6 +341,7 @@ struct Drain {
     int pos, rem;     // next bin, bins left
     float t;          // pos - ks (bin offset from the closest approach)
     float ga, al;     // log2 value(t) = ga t^2 + al   (noocl: al includes log2 w [+ log2 sin theta])
+    float t2, ga2, al2;   // twin drain: the second ray of the lane (al2 = kNoTwin: none), see fx_twin_setup
     float st;         // sin(theta_i) (kept separate only when per-ray outputs are written)
     float sc, wc, T;      // netf: sigma c dT, w c dT, transmittance T at pos (linear: one exp per bin)
     float beta, xlo, elo; // binint: dr sqrt(a/2), lower bin edge beta (kap - 1/2) and erfc(|xlo|)
@@ -391,7 +401,9 @@ __device__ __forceinline__ bool drain_setup(const float* A, const float* u0, flo
 // to the ray queue ring at qbase + cnt.  Branch-free body (every lane evaluates a clamped
 // candidate, `more` masks the result), two candidates per trip so their table reads overlap;
 // returns once cnt >= 64 or every lane exhausted its box (cnt < 64 + 2*64 <= kRQ on return).
-template <bool DENSE, bool REC = false>
+// TWIN (forward only): two candidates of one trip that are the adjacent cells (i, j) and (i, j + 1) and both
+// pass become ONE entry flagged kTwinBit (a cell joins at most one twin), so a trip appends at most NC entries.
+template <bool DENSE, bool REC = false, bool TWIN = false>
 __device__ __forceinline__ void enumerate_box(const float* M, int i1, int j0, int j1, bool& more, int& ci, int& cj,
                                               const float2* tth, const float2* tph, int nt1, unsigned* rayq,
                                               int qbase, int& cnt, unsigned long long* rec0 = nullptr,
@@ -432,6 +444,17 @@ __device__ __forceinline__ void enumerate_box(const float* M, int i1, int j0, in
         unsigned es[NC];
 #pragma unroll
         for (int u = 0; u < NC; ++u) es[u] = pack_ray(lane, cis[u], cjs[u]);
+        if (TWIN) {
+            bool covered = false;   // cell u is the second ray of the twin that cell u - 1 opened
+#pragma unroll
+            for (int u = 0; u < NC; ++u) {
+                const bool open = !covered && pass[u] && u + 1 < NC && pass[u + 1 < NC ? u + 1 : u] &&
+                                  cis[u + 1 < NC ? u + 1 : u] == cis[u];
+                pass[u] = pass[u] && !covered;
+                es[u] |= open ? kTwinBit : 0u;
+                covered = open;
+            }
+        }
         {
             const bool wrap = cjs[NC - 1] >= j1;
             cj = wrap ? j0 : cjs[NC - 1] + 1;
@@ -586,7 +609,11 @@ __device__ __forceinline__ void fx_gadd(unsigned long long* at, float v) {
     __hip_atomic_fetch_add(at, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// a lane without a second ray: al2 = kNoTwin makes every value of the second recurrence exp2(-200) = 0
+constexpr float kNoTwin = -200.f;
 // FX refill placement (see kFxShift): newl = this lane took a new segment, act = it holds one
+// (TW: a lane's twin moves both rays, so its reach is the shorter of the two)
+template <bool TW = false>
 __device__ __forceinline__ void fx_place(bool newl, bool act, Drain& d) {
     if (!__builtin_amdgcn_ballot_w64(newl)) return;
     const int pb = d.pos >> 1, ph = pb & 15, o = d.pos & 1;
@@ -594,7 +621,12 @@ __device__ __forceinline__ void fx_place(bool newl, bool act, Drain& d) {
     // reach: the seed exponent at the new start stays >= -100 (no flush to zero), the start >= bin 0
     const float span = d.al + 100.f;
     const float tm = span > 0.f ? __builtin_amdgcn_sqrtf(span * __builtin_amdgcn_rcpf(fmaxf(-d.ga, 1e-30f))) : 0.f;
-    const int smax = newl ? min(min(kFxShift, pb), (int)floorf(0.5f * (d.t - (float)o + tm))) : -1;
+    int smax = newl ? min(min(kFxShift, pb), (int)floorf(0.5f * (d.t - (float)o + tm))) : -1;
+    if (TW && d.al2 > kNoTwin) {
+        const float span2 = d.al2 + 100.f;
+        const float tm2 = span2 > 0.f ? __builtin_amdgcn_sqrtf(span2 * __builtin_amdgcn_rcpf(fmaxf(-d.ga2, 1e-30f))) : 0.f;
+        smax = min(smax, (int)floorf(0.5f * (d.t2 - (float)o + tm2)));
+    }
     bool pend = newl && smax >= 0;
     int sh = 0;
 #pragma unroll
@@ -615,46 +647,7 @@ __device__ __forceinline__ void fx_place(bool newl, bool act, Drain& d) {
         d.pos -= delta;
         d.rem += delta;
         d.t -= (float)delta;
-    }
-}
-
-// FX refill balance (no-occlusion FX drain, with the deal below).  The deal leaves a group cost of about
-// ceil(c / 4) for a residue held by c segments, so the largest residue count sets the ds_add_u64 conflicts
-// (scripts/fx_counts.py).  At refill each new segment may start up to kFxShift words early (exact Gaussian
-// values before its support, as fx_place): it takes the smallest shift whose residue holds fewer than
-// ceil(active / 16) segments, claimed with a wave-private LDS counter per residue (ds_add_rtn; a claim past
-// the cap is undone and the next shift tried; none free: no shift).  Placement affects only conflicts.
-__device__ __forceinline__ void fx_balance(bool newl, bool act, Drain& d, unsigned* cnt) {
-    const int lane = lane_id();
-    if (lane < 16) cnt[lane] = 0u;
-    wave_sync();
-    const int pb = d.pos >> 1, o = d.pos & 1;
-    if (act && !newl)
-        __hip_atomic_fetch_add(cnt + (pb & 15), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-    wave_sync();
-    const unsigned cap = (unsigned)((__popcll(__builtin_amdgcn_ballot_w64(act)) + 15) >> 4);
-    // reach: the seed exponent at the new start stays >= -100 (no flush to zero), the start >= bin 0
-    const float span = d.al + 100.f;
-    const float tm = span > 0.f ? __builtin_amdgcn_sqrtf(span * __builtin_amdgcn_rcpf(fmaxf(-d.ga, 1e-30f))) : 0.f;
-    const int smax = newl ? min(min(kFxShift, pb), (int)floorf(0.5f * (d.t - (float)o + tm))) : -1;
-    int sh = -1;
-#pragma unroll
-    for (int s2 = 0; s2 <= kFxShift; ++s2) {
-        const bool tryit = newl && sh < 0 && s2 <= smax;
-        if (!__builtin_amdgcn_ballot_w64(tryit)) break;
-        if (tryit) {
-            unsigned* c = cnt + ((pb - s2) & 15);
-            const unsigned v = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-            if (v < cap) sh = s2;
-            else __hip_atomic_fetch_add(c, 0xFFFFFFFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-        }
-    }
-    wave_sync();
-    if (sh > 0) {
-        const int delta = o + 2 * sh;
-        d.pos -= delta;
-        d.rem += delta;
-        d.t -= (float)delta;
+        if (TW) d.t2 -= (float)delta;
     }
 }
 
@@ -667,15 +660,8 @@ __device__ __forceinline__ void fx_balance(bool newl, bool act, Drain& d, unsign
 // group, the least any assignment can reach) and the active lanes spread evenly over the groups.  The sort is
 // bit-serial over ballots (5 key bits, no per-residue tables); the state moves with ds_permute (a bijection).
 // The per-lane headroom sums (fxs) stay: their total still bounds every field.
-#ifndef NLOSGR_FX_DIAG_NOCONFLICT
-#define NLOSGR_FX_DIAG_NOCONFLICT 0
-#endif
 constexpr bool kFxPerm = NLOSGR_FXPERM != 0;   // (defaults with FwdLayout above)
-#ifndef NLOSGR_FXPERM_NETF
-#define NLOSGR_FXPERM_NETF 0   // measured: netf fwd 894.5 vs 884.5 ms without (its drain is less LDS-bound)
-#endif
-constexpr bool kFxPermNetf = NLOSGR_FXPERM_NETF != 0;
-template <int MODE>
+template <int MODE, bool TW = false>
 __device__ __forceinline__ void fx_perm(bool& newl, bool& act, Drain& d, float& fpk) {
     const unsigned res = (unsigned)((d.pos >> 1) & 15);
     // deal: sorted by (residue, lane), idle lanes last; position s -> lane 16 (s mod 4) + s / 4
@@ -701,6 +687,11 @@ __device__ __forceinline__ void fx_perm(bool& newl, bool& act, Drain& d, float& 
     if (MODE == NLOSGR_MODE_NETF) {   // the segment's transmittance (carrying its weight) and sigma c dT
         d.T = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.T)));
         d.sc = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.sc)));
+    }
+    if (TW) {   // the lane's second ray
+        d.t2 = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.t2)));
+        d.ga2 = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.ga2)));
+        d.al2 = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.al2)));
     }
     act = ri2 != 0;
     newl = (ri2 >> 30) & 1;
@@ -826,7 +817,90 @@ __device__ __forceinline__ void tail_round(const Drain& d, const float t, float&
     }
 }
 
-template <int PRESET, int MODE, bool DENSE, bool RAYS, bool CACHE, bool TAIL, bool FX, bool BR = false>
+// Twin drain (TW; the no-occlusion FX forward with the refill deal, the training hot path).  The forward is
+// paced by the number of ds_add_u64 it issues, and that number is set by rays: a lane that drains the two
+// adjacent cells (i, j), (i, j + 1) of one pair at once sums their values in registers and issues one add for
+// both.  The two segments' closest-approach bins are a few bins apart, so their union is little longer than
+// either (scripts/twin_estimate.py), and both setups share the pair's shuffled A, u0, lw.
+// The lane walks the union [min kl, max kh]; each ray's recurrence is seeded at the round's first bin from its
+// own (t, ga, al).  Outside its own support a ray adds its exact Gaussian values (< exp(-m_c^2 / 2) of its peak,
+// the same tail the TAIL rounds add past a segment's end), provided its seed does not flush to zero before
+// its centre (the rest of the round would be lost) and its ratio does not overflow (0 x inf): both rays must
+// satisfy fx_place's condition at the union's first bin, seed exponent >= -100 and ratio exponent <= 120.  A
+// seed that is fine there is fine at every later round start before the centre (|t| only shrinks).  A twin
+// that fails is split: the lane keeps the first ray and the second goes back to the queue as a single entry.
+// Returns 0: no segment, 1: one ray, 2: twin, 3: split (d holds the first ray).  pk = the sum of the peaks
+// (units).  The work counts (nlosgr_count_support) are not kept here: a counting launch never takes the FX drain.
+__device__ __forceinline__ bool fx_seed_ok(float ga, float al, float t) {
+    return fmaf(ga, t * t, al) >= -100.f && ga * fmaf(2.f, t, 1.f) <= 120.f;
+}
+__device__ __forceinline__ int fx_twin_setup(const float* A, const float* u0, float lw, float2 th, float2 pha,
+                                             float2 phb, bool twin, int nr, float mc2, float r0, float dr,
+                                             float inv_dr, Drain& d, float& pk) {
+    Ray Ra, Rb;
+    bool gota = ray_setup<false>(A, u0, th.x * pha.x, th.x * pha.y, th.y, mc2, r0, inv_dr, nr, Ra);
+    bool gotb = twin && ray_setup<false>(A, u0, th.x * phb.x, th.x * phb.y, th.y, mc2, r0, inv_dr, nr, Rb);
+    if (!gota && gotb) {   // only the second cell has bins: it is the lane's one ray
+        Ra = Rb;
+        gota = true;
+        gotb = false;
+    }
+    if (!gota) return 0;
+    const float lst = flog2(th.x);
+    d.pos = Ra.kl;
+    d.rem = Ra.kh - Ra.kl + 1;
+    d.t = (float)Ra.kl - Ra.ks;
+    d.ga = -kHalfLog2e * Ra.a * dr * dr;   // (the expressions of drain_setup: a single is bit-identical to it)
+    d.al = fmaf(-kHalfLog2e, Ra.m2min, lw) + lst;
+    d.t2 = 0.f; d.ga2 = 0.f; d.al2 = kNoTwin;
+    pk = fast_exp2(d.al);
+    if (!gotb) return 1;
+    const float gb = -kHalfLog2e * Rb.a * dr * dr, ab =fmaf(-kHalfLog2e, Rb.m2min, lw) + lst;
+    const int pos = min(Ra.kl, Rb.kl), end = max(Ra.kh, Rb.kh);
+    const float ta = (float)pos - Ra.ks, tb = (float)pos - Rb.ks;
+    if (!(fx_seed_ok(d.ga, d.al, ta) && fx_seed_ok(gb, ab, tb))) return 3;
+    d.pos = pos;
+    d.rem = end - pos + 1;
+    d.t = ta;
+    d.t2 = tb; d.ga2 = gb; d.al2 = ab;
+    pk += fast_exp2(ab);
+    return 2;
+}
+// one TAIL round of a twin lane (tail_round's no-occlusion body with two recurrences): slot 0 before pos adds
+// 0; every pair of bins emits the two rays' sums
+template <class Emit>
+__device__ __forceinline__ void tail_round_twin(const Drain& d, Emit&& emit) {
+    const int o = d.pos & (kVW - 1);
+    float cur = fast_exp2(fmaf(d.ga, d.t * d.t, d.al));
+    float q = fast_exp2(d.ga * fmaf(2.f, d.t, 1.f));
+    const float cc = fast_exp2(2.f * d.ga);
+    float cur2 = fast_exp2(fmaf(d.ga2, d.t2 * d.t2, d.al2));
+    float q2 = fast_exp2(d.ga2 * fmaf(2.f, d.t2, 1.f));
+    const float cc2 = fast_exp2(2.f * d.ga2);
+#pragma unroll
+    for (int kv = 0; kv < kStepsTwin / kVW; ++kv) {
+        const float v0 = (kv == 0 && o) ? 0.f : cur + cur2;
+        if (kv == 0) {
+            cur = o ? cur : cur * q;
+            q = o ? q : q * cc;
+            cur2 = o ? cur2 : cur2 * q2;
+            q2 = o ? q2 : q2 * cc2;
+        } else {
+            cur *= q;
+            q *= cc;
+            cur2 *= q2;
+            q2 *= cc2;
+        }
+        const float v1 = cur + cur2;
+        cur *= q;
+        q *= cc;
+        cur2 *= q2;
+        q2 *= cc2;
+        emit(kv, v0, v1);
+    }
+}
+
+template <int PRESET, int MODE, bool DENSE, bool RAYS, bool CACHE, bool TAIL, bool FX, bool BR = false, bool TW = false>
 __device__ __forceinline__ void fwd_body(const KArgs& k) {
     extern __shared__ __align__(16) float smem[];
     const int nr = k.geo.nr, nt = k.geo.nt, np_ = k.geo.np;
@@ -852,7 +926,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
         tth[t] = make_float2(k.geo.sin_theta[(size_t)p * nt + t], k.geo.cos_theta[(size_t)p * nt + t]);
     for (int t = threadIdx.x; t < np_; t += blockDim.x)
         tph[t] = make_float2(k.geo.cos_phi[(size_t)p * np_ + t], k.geo.sin_phi[(size_t)p * np_ + t]);
-    for (int t = lane; t < (FX ? nr + kSteps + 4 : nr + 2 * kSteps + 64); t += 64) hist[t] = 0.f;
+    for (int t = lane; t < (FX ? nr + kStepsPad + 4 : nr + 2 * kStepsPad + 64); t += 64) hist[t] = 0.f;
     __syncthreads();
 
     const float px = k.geo.wall[3 * p], py = k.geo.wall[3 * p + 1], pz = k.geo.wall[3 * p + 2];
@@ -873,12 +947,12 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
     float fpk = 0.f, fxs = 0.f;     // this lane's segment peak, and its peaks since the last check
     unsigned long long* const grow = FX ? k.hfx + (size_t)p * nr : nullptr;
     unsigned* hist32 = reinterpret_cast<unsigned*>(hist);
-    const int nfx = nr + kSteps + 2;   // fields a round can reach (bins past nr are pad)
+    const int nfx = nr + kStepsPad + 2;   // fields a round can reach (bins past nr are pad)
     // the float2 drain (two bins per LDS read-add-write; claim keys on bin pairs)
     constexpr bool QUADF = (MODE == NLOSGR_MODE_NOOCL || ((MODE == NLOSGR_MODE_NETF || MODE == NLOSGR_MODE_BININT) && TAIL)) &&
                            !RAYS && !DENSE;
-    const int pad = nr + kSteps + lane;       // this lane's private pad bins (non-winners)
-    const int padq = al4(nr + kSteps);        // quad drain: one pad quad row shared by non-winners (they add 0)
+    const int pad = nr + kStepsPad + lane;       // this lane's private pad bins (non-winners)
+    const int padq = al4(nr + kStepsPad);        // quad drain: one pad quad row shared by non-winners (they add 0)
     unsigned npair = 0, nseg = 0;
     unsigned long long nsamp = 0;
 
@@ -890,6 +964,10 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
     d.sc = 0.f; d.wc = 0.f; d.T = 0.f; d.rbase = 0;
     d.beta = 0.f; d.xlo = 0.f; d.elo = 0.f;
     d.wrap = 0; d.tw = 0.f;
+    d.t2 = 0.f; d.ga2 = 0.f; d.al2 = kNoTwin;
+    static_assert(!TW || (FX && !BR && !CACHE && kFxPerm && MODE == NLOSGR_MODE_NOOCL),
+                  "twin drain: the no-occlusion FX forward with the refill deal only");
+    unsigned ntwin = 0, nsplit = 0;   // TW: twins drained as one segment / split at the merge guard (wave-uniform)
     bool act = false;
     int qhead = 0, qcount = 0;
 
@@ -930,7 +1008,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
         while (true) {
             if (qcount < 64 && __builtin_amdgcn_ballot_w64(more)) {
                 wave_sync();
-                enumerate_box<DENSE, CACHE>(P.M, P.i1, P.j0, P.j1, more, ci, cj, tth, tph, nt - 1, rayq, qhead,
+                enumerate_box<DENSE, CACHE, TW>(P.M, P.i1, P.j0, P.j1, more, ci, cj, tth, tph, nt - 1, rayq, qhead,
                                             qcount, &crec0, &crec1, &ccell);
                 wave_sync();
             }
@@ -939,14 +1017,13 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
             const int nidle = __popcll(idle);
             // the no-occlusion FX drain refills later: the deal's cost is per refill (REFILL 48 / 52 / 56 / 60 / 62:
             // 745.9 / 735.7 / 732.4 / 736.7 / 745.4 ms, same box)
-            constexpr int kRef = (FX && !BR && ((kFxPerm && MODE == NLOSGR_MODE_NOOCL) ||
-                                                (kFxPermNetf && MODE == NLOSGR_MODE_NETF))) ? kRefillFx : kRefill;
+            constexpr int kRef = (FX && !BR && kFxPerm && MODE == NLOSGR_MODE_NOOCL) ? kRefillFx : kRefill;
             if (qcount > 0 && (nidle >= kRef || !anymore)) {
                 // idle lane of rank r takes queue entry qhead + r; pair data come from lane `slot`
                 const int r = lanes_below(idle);
                 const bool take = !act && r < qcount;
                 const unsigned e = take ? rayq[(qhead + r) & (kRQ - 1)] : 0u;
-                const int slot = e & 0xFF, i = (e >> 8) & 0xFFF, j = e >> 20;
+                const int slot = e & (TW ? 0x3F : 0xFF), i = (e >> 8) & 0xFFF, j = e >> 20;
                 float A[9], u0[3];
 #pragma unroll
                 for (int c = 0; c < 9; ++c) A[c] = __shfl(P.A[c], slot);
@@ -956,7 +1033,23 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                 const float scs = MODE == NLOSGR_MODE_NETF ? __shfl(sc, slot) : 0.f;
                 const float wcs = MODE == NLOSGR_MODE_NETF ? __shfl(wc, slot) : 0.f;
                 bool got = false;
-                if (take && !(flags & 1)) {
+                int tcode = 0;   // TW: fx_twin_setup's result
+                if (TW) {
+                    if (take && !(flags & 1)) {
+                        const bool twin = (e & kTwinBit) != 0u;
+                        float pk = 0.f;
+                        // (j + 1 <= j1 < np for a twin entry; a single reads its own cell twice)
+                        tcode = fx_twin_setup(A, u0, lws, tth[i], tph[j], tph[twin ? j + 1 : j], twin, nr, mc2, r0, dr,
+                                              inv_dr, d, pk);
+                        got = tcode != 0;
+                        if ((flags & NLOSGR_FLAG_FX_TWIN_STATS) && tcode == 2) atomicMax(k.fx_info + 7, d.rem);
+                        act = got && !(flags & 4);
+                        if (act) {
+                            fpk = pk;   // the sum of the two peaks: the most the lane adds to any bin
+                            fxs += fpk;
+                        }
+                    }
+                } else if (take && !(flags & 1)) {
                     // dense: consecutive queue entries start 37 bins apart (distinct claim keys)
                     const int stag = dense_wrap<MODE, DENSE>() ? (int)(((unsigned)(qhead + r) * 37u) % (unsigned)nr) : 0;
                     got = drain_setup<MODE, DENSE, RAYS>(A, u0, lws, scs, wcs, tth[i], tph[j], i, j, np_, nr, mc2,
@@ -975,16 +1068,25 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                 const int ntake = min(nidle, qcount);
                 qhead = (qhead + ntake) & (kRQ - 1);
                 qcount -= ntake;
+                if (TW) {
+                    const unsigned long long tm = __builtin_amdgcn_ballot_w64(tcode == 2);
+                    const unsigned long long sm = __builtin_amdgcn_ballot_w64(tcode == 3);
+                    ntwin += (unsigned)__popcll(tm);
+                    if (sm) {
+                        // split twins: the second ray returns to the queue's tail as a single entry (the queue
+                        // just gave up ntake >= popc(sm) entries, so the ring cannot overflow)
+                        if (tcode == 3) rayq[(qhead + qcount + lanes_below(sm)) & (kRQ - 1)] = pack_ray(slot, i, j + 1);
+                        qcount += __popcll(sm);
+                        nsplit += (unsigned)__popcll(sm);
+                        wave_sync();
+                    }
+                }
                 // (netf keeps its start: its transmittance would have to be re-seeded)
                 bool newl = take && act;
-                if (FX && !BR && NLOSGR_FXBAL && kFxPerm && kFxShift > 0 && MODE == NLOSGR_MODE_NOOCL)
-                    fx_balance(newl, act, d, reinterpret_cast<unsigned*>(hist + al4(nr + kSteps + 4)));
-                // netf has no refill placement (its transmittance would need re-seeding); the deal is opt-in
-                // there too (NLOSGR_FXPERM_NETF)
-                if (FX && !BR && ((kFxPerm && MODE == NLOSGR_MODE_NOOCL) || (kFxPermNetf && MODE == NLOSGR_MODE_NETF)))
-                    fx_perm<MODE>(newl, act, d, fpk);
-                if (FX && !BR && kFxShift > 0 && MODE != NLOSGR_MODE_NETF && !(NLOSGR_FXBAL && kFxPerm && MODE == NLOSGR_MODE_NOOCL))
-                    fx_place(newl, act, d);
+                // netf has neither the deal (measured slower: its drain is less LDS-bound) nor the refill
+                // placement (its transmittance would need re-seeding)
+                if (FX && !BR && kFxPerm && MODE == NLOSGR_MODE_NOOCL) fx_perm<MODE, TW>(newl, act, d, fpk);
+                if (FX && !BR && kFxShift > 0 && MODE != NLOSGR_MODE_NETF) fx_place<TW>(newl, act, d);
             }
             const bool anyact = __builtin_amdgcn_ballot_w64(act) != 0;
             if (!anyact) {
@@ -1066,11 +1168,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                 const int lim = remw + o;   // slot j is in the segment iff o <= j < lim
                 if (TAIL && win) {
                     // (FX: every emitting lane is a winner, so its row starts at the even bin with no loser select)
-#if NLOSGR_FX_DIAG_NOCONFLICT   // diagnostics (wrong sums): every lane on its own word residue, no bank conflicts
-                    float2* const hbw = reinterpret_cast<float2*>(FX ? hist + 2 * lane : hb);
-#else
                     float2* const hbw = reinterpret_cast<float2*>(FX ? hist + (d.pos & ~(VW - 1)) : hb);
-#endif
                     if (BR) {   // bright launch: u64 integer adds straight into the wall point's global row
                         const int gb0 = d.pos & ~(VW - 1);
                         tail_round<MODE>(d, t, T, [&](int kv, float v0, float v1) {
@@ -1078,6 +1176,8 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                             if (b < nr && v0 > 0.f) fx_gadd(grow + b, v0);
                             if (b + 1 < nr && v1 > 0.f) fx_gadd(grow + b + 1, v1);
                         });
+                    } else if (TW) {   // both rays of the lane in one ds_add_u64 per two bins
+                        tail_round_twin(d, [&](int kv, float v0, float v1) { emit2<FX>(hbw + kv, v0, v1); });
                     } else {
                         tail_round<MODE>(d, t, T, [&](int kv, float v0, float v1) { emit2<FX>(hbw + kv, v0, v1); });
                     }
@@ -1109,7 +1209,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                         compiler_fence();
                     }
                 }
-                t += (float)(fsteps<MODE>() - o);
+                t += (float)(fsteps<MODE, TW>() - o);
             } else {
             // netf, culled: pdf by the exp2 recurrence (kRecurrence), re-seeded per round
             constexpr bool REC = MODE == NLOSGR_MODE_NETF && !DENSE;
@@ -1168,8 +1268,9 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
             }
             }
             if (win) {
-                const int adv = QUAD ? fsteps<MODE>() - (d.pos & (VW - 1)) : fsteps<MODE>();
+                const int adv = QUAD ? fsteps<MODE, TW>() - (d.pos & (VW - 1)) : fsteps<MODE, TW>();
                 d.t = t;
+                if (TW) d.t2 += (float)(fsteps<MODE, TW>() - (d.pos & (VW - 1)));
                 d.T = T;
                 d.xlo = xlo;
                 d.elo = elo;
@@ -1196,7 +1297,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
         }
         if (!have) break;
     }
-    if (k.counts) {
+    if (!TW && k.counts) {
         unsigned long long ns = nsamp;
         for (int o = 32; o > 0; o >>= 1) ns += __shfl_xor(ns, o);
         if (lane == 0) {
@@ -1209,6 +1310,10 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
     if (lane == 0)
         for (int c = 0; c < 5; ++c) atomicAdd(&g_fdbg[c], fdbg[c]);
 #endif
+    if (TW && lane == 0) {   // twins formed / split (nlosgr_fx_info)
+        if (ntwin) atomicAdd(k.fx_info + 5, (int)ntwin);
+        if (nsplit) atomicAdd(k.fx_info + 6, (int)nsplit);
+    }
     if (BR) {   // bright segments taken (nlosgr_fx_info)
         if (lane == 0 && nseg) atomicAdd(k.fx_info + 3, (int)nseg);
         return;
@@ -1235,9 +1340,10 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
     }
 }
 
-template <int PRESET, int MODE, bool DENSE, bool RAYS, bool CACHE, bool TAIL = false, bool FX = false>
+// TW: the twin drain (fx_twin_setup), the default of the no-occlusion FX forward
+template <int PRESET, int MODE, bool DENSE, bool RAYS, bool CACHE, bool TAIL = false, bool FX = false, bool TW = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6, 8))) void fwd_kernel(KArgs k) {
-    fwd_body<PRESET, MODE, DENSE, RAYS, CACHE, TAIL, FX>(k);
+    fwd_body<PRESET, MODE, DENSE, RAYS, CACHE, TAIL, FX, false, TW>(k);
 }
 // FX bright launch (BR): the Gaussians whose amplitude bound reaches 2^kFxBits units (fx_blist_kernel), every
 // segment added as u64 integers straight into the wall point's global row (kFxBits); usually an empty list
@@ -2513,7 +2619,15 @@ void launch_fwd(const KArgs& ka, size_t shm, hipStream_t s) {
     if constexpr ((MODE == NLOSGR_MODE_NOOCL || MODE == NLOSGR_MODE_NETF || MODE == NLOSGR_MODE_BININT) && !DENSE &&
                   !RAYS && !CACHE) {
         if (ka.hfx) {   // run_fwd decided the fixed-point TAIL drain (fx_eligible)
-            hipLaunchKernelGGL((fwd_kernel<PRESET, MODE, DENSE, RAYS, CACHE, true, true>), grid, dim3(kBlock), shm, s, ka);
+            // the no-occlusion drain takes two adjacent rays of a pair per lane (NLOSGR_FLAG_FX_NOTWIN: one)
+            bool twin = false;
+            if constexpr (MODE == NLOSGR_MODE_NOOCL && kFxPerm) {
+                twin = !(ka.opt.flags & NLOSGR_FLAG_FX_NOTWIN);
+                if (twin)
+                    hipLaunchKernelGGL((fwd_kernel<PRESET, MODE, DENSE, RAYS, CACHE, true, true, true>), grid, dim3(kBlock), shm, s, ka);
+            }
+            if (!twin)
+                hipLaunchKernelGGL((fwd_kernel<PRESET, MODE, DENSE, RAYS, CACHE, true, true>), grid, dim3(kBlock), shm, s, ka);
             // the bright Gaussians' launch (one split per wall point; its list is usually empty)
             hipLaunchKernelGGL((fx_bright_kernel<PRESET, MODE>), dim3(ka.geo.nwall, 1), dim3(kBlock), shm, s, ka);
             return;
@@ -2700,6 +2814,10 @@ int run_fwd(const nlosgr_gaussians* g, const nlosgr_geometry* geo, const nlosgr_
         ka.hpart = (float*)fpart;
         ka.nfsplit = nfs;
     }
+    // a forward that does not take the FX drain leaves nlosgr_fx_info all zeros, not an earlier forward's words
+    // (the FX tail lies past the float partials)
+    if (!fx && g->ng > 0)
+        HIPCHK(hipMemsetAsync(fpart + fx_tail_off(g, geo) + kFxBins * sizeof(unsigned), 0, 8 * sizeof(int), s));
     if (g->ng > 0) {
         // (FX: the bright Gaussians get a negative sigma in the records, see preprocess_kernel)
         launch_preprocess(g, (GaussRec*)workspace, s, ka.hfx ? ka.fx_bound : nullptr, ka.fx_info);
@@ -2822,7 +2940,7 @@ int nlosgr_fx_info(const nlosgr_gaussians* g, const nlosgr_geometry* geo, const 
     if (tiles_engine(opt) || g->ng == 0) return set_err(NLOSGR_E_UNSUPPORTED, "fx_info: pair-major forward with ng > 0");
     const char* fpart = fpart_ptr(g, geo, opt, const_cast<void*>(workspace));
     const char* info = fpart + fx_tail_off(g, geo) + kFxBins * sizeof(unsigned);
-    HIPCHK(hipMemcpyAsync(info_out, info, 4 * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+    HIPCHK(hipMemcpyAsync(info_out, info, 8 * sizeof(int32_t),hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
     return NLOSGR_OK;
 }
 

@@ -64,7 +64,7 @@ class AdamGroup(ctypes.Structure):
 
 ADAM_MAX_GROUPS = 8  # NLOSGR_ADAM_MAX_GROUPS
 MAX_PER_RAY = 256   # NLOSGR_MAX_PER_RAY
-ABI_VERSION = 9     # NLOSGR_ABI_VERSION
+ABI_VERSION = 10    # NLOSGR_ABI_VERSION
 
 # nlosgr_options.flags variant selection (NLOSGR_FLAG_*; A/B timing and parity cross-checks, 0 in production)
 FLAG_FLOAT_DRAIN = 0x100   # forward: fp32 claim drain instead of the fixed-point drain
@@ -75,6 +75,8 @@ FLAG_BWD_SHARED = 0x1000   # backward: shared-row layout
 FLAG_BWD_PERWAVE = 0x2000  # backward: per-wave row layout
 FLAG_FX_MAXUNIT = 0x4000   # FX drain unit from the largest bound (round-5 rule; diagnostics)
 FLAG_TILE_NOBIN = 0x8000   # ray-tile engine: in-kernel cull instead of the tile bins (A/B)
+FLAG_FX_NOTWIN = 0x10000   # no-occlusion FX drain: one ray per lane instead of two adjacent rays (A/B, tests)
+FLAG_FX_TWIN_STATS = 0x20000  # twin drain: record the longest twin in fx_info (diagnostics, slow)
 
 # every symbol include/nlosgr.h declares (tests check the exports against this list)
 EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "nlosgr_count_support", "nlosgr_fx_info",

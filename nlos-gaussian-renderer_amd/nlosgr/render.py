@@ -155,15 +155,16 @@ def render_backward(mu, scaling, rotation, opacity, features, geo, cfg, grad_his
 
 def fx_info(mu, scaling, rotation, opacity, features, geo, cfg, workspace):
     """The fixed-point forward's state after render_forward(..., workspace=workspace) with the same inputs:
-    (E, E of the largest amplitude bound, LDS flushes, bright segments); zeros when the forward did not
-    take the fixed-point drain (nlosgr_fx_info)."""
+    (E, E of the largest amplitude bound, LDS flushes, bright segments, twins drained as one segment, twins
+    split at the merge guard, longest twin in bins under FLAG_FX_TWIN_STATS); zeros when the forward did not take the fixed-point drain (nlosgr_fx_info)."""
     lib = _lib.load()
     dev = mu.device
     mu, scaling, rotation, opacity, features = [_as_f32(t) for t in (mu, scaling, rotation, opacity, features)]
     g, gs, o = _structs(mu, scaling, rotation, opacity, features, geo, cfg)
-    out = torch.zeros(4, dtype=torch.int32, device=dev)
+    out = torch.zeros(8, dtype=torch.int32, device=dev)
     _lib.check(lib.nlosgr_fx_info(g, gs, o, _lib.ptr(workspace), _lib.ptr(out), _lib.stream_handle(dev)))
-    return tuple(int(v) for v in out.cpu())
+    v = [int(x) for x in out.cpu()]
+    return (v[0], v[1], v[2], v[3], v[5], v[6], v[7])
 
 
 def workspace_for(mu, scaling, rotation, opacity, features, geo, cfg, ray_cache=False):
