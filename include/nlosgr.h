@@ -24,6 +24,9 @@
  *   nlosgr_voxelize     <- evaluation() -> gaussian2volume main.py:374-387, nlos_helpers.py:40-69, with the
  *                          two sums of estimate_rho_w_no_occlusion(out_separately=True)
  *                          gaussian_model/gaussian_model.py:346-364 on a regular voxel grid
+ *   nlosgr_mesh_*       <- gaussian2volume(mode='mesh') nlos_helpers.py:50-69: the surface of the density at
+ *                          its mean (:51), as an isosurface (marching tetrahedra) in place of the open3d
+ *                          Poisson reconstruction
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -41,7 +44,7 @@
 extern "C" {
 #endif
 
-#define NLOSGR_ABI_VERSION 10
+#define NLOSGR_ABI_VERSION 11
 
 /* convention presets */
 enum {
@@ -343,6 +346,56 @@ NLOSGR_API int nlosgr_voxelize(const nlosgr_gaussians* g, const nlosgr_voxel_gri
  * the two remaining axes in their original order. */
 NLOSGR_API int nlosgr_volume_project(const float* vol, int32_t nx, int32_t ny, int32_t nz, int32_t axis,
                           float* max_out, int32_t* argmax_out, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Surface output (ABI 11): the isosurface {x : vol(x) = level} of a regular-grid volume as an indexed
+ * triangle mesh.  It stands where the reference has gaussian2volume(mode='mesh') (nlos_helpers.py:50-69):
+ * the same threshold (the caller passes the density's mean, :51), with an isosurface in place of the
+ * open3d Poisson reconstruction.  Marching tetrahedra on the Kuhn decomposition (6 tetrahedra per cell,
+ * translation invariant, so the index topology is watertight); no atomics, a fixed output order, two runs
+ * bitwise equal.
+ *   inside      grid point p is inside iff isfinite(vol) && vol >= level (NaN, +-inf: outside)
+ *   edges       p owns p -> p + d, d0..d6 = (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1), where the
+ *               far end is in the grid; an edge crosses when exactly one end is inside
+ *   vertices    one per crossing edge, numbered by owner index (ix*ny + iy)*nz + iz, then d.  With fa, fb at
+ *               the owner and the far end: t = (level - fa) / (fb - fa) in fp32, 0.5 if either is not finite;
+ *               position (1-t) xa + t xb per axis from the tables (fmaf; exactly the end point at t = 0 / 1),
+ *               value (1-t) aa + t ab, normal -normalize((1-t) ga + t gb) with g the central difference
+ *               (f[i+1] - f[i-1]) / (x[i+1] - x[i-1]) per axis, one-sided at the ends; (0,0,0) when that
+ *               vector has zero or non-finite length.  Normals point from high values to low.
+ *   tetrahedra  cell p (ix < nx-1, iy < ny-1, iz < nz-1), tau = 0..5 over the axis permutations (a,b,c) in
+ *               lexicographic order: v0 = p, v1 = v0 + e_a, v2 = v1 + e_b, v3 = p + (1,1,1); mask bit i: v_i inside
+ *   triangles   (XY = the vertex on edge v_X v_Y) one inside A, outside O1<O2<O3: (AO1, AO2, AO3); three
+ *               inside I1<I2<I3, outside D: (I1D, I2D, I3D); two inside A<B, outside C<D: (AC, AD, BD),
+ *               (AC, BD, BC); the last two vertices swapped where the same triangle through the edge
+ *               midpoints of the unit cell would face the inside corners, so every non-degenerate triangle
+ *               is counter-clockwise seen from the low side.  Numbered by cell index
+ *               (ix*(ny-1) + iy)*(nz-1) + iz, then tau, then the order above; int32 indices.
+ * A corner value equal to `level` gives t = 0 or 1, coincident vertices and zero-area triangles, which are
+ * kept: the index topology stays manifold.  Any extent < 2: the mesh is empty.
+ * The tables of the grid are read as given (ascending, not assumed uniform).
+ * Two calls with one host read of counts_out between them (the library neither allocates nor synchronises).
+ * ------------------------------------------------------------------------------------- */
+
+/* Scratch bytes for nlosgr_mesh_count / nlosgr_mesh_emit (host only; 0 with a message in nlosgr_last_error on
+ * invalid extents or NULL tables): 12 B per grid point plus block sums. */
+NLOSGR_API size_t nlosgr_mesh_workspace_bytes(const nlosgr_voxel_grid* grid);
+
+/* Classifies every grid point and scans the counts into `workspace` (reduce per block / scan of the block
+ * sums / add back: three launches, no workgroup waits on another).  counts_out: DEVICE [2] = {nverts, ntris},
+ * 64-bit totals; the per-point offsets kept in the workspace are 32-bit. */
+NLOSGR_API int nlosgr_mesh_count(const float* vol, const nlosgr_voxel_grid* grid, float level, void* workspace,
+                      long long* counts_out, void* hip_stream);
+
+/* Writes the mesh nlosgr_mesh_count counted (same vol, grid, level, workspace).  attr (may be NULL): a second
+ * volume of the same shape to interpolate a per-vertex value from.  verts_out [nverts,3], normals_out
+ * [nverts,3] (may be NULL), attr_out [nverts] (NULL iff attr is NULL), tris_out [ntris,3].
+ * nverts or ntris above 2^31 - 1: NLOSGR_E_UNSUPPORTED.  Counts that disagree with the workspace's totals
+ * cannot be seen by the host without a synchronisation: the kernels then write nothing, and no kernel ever
+ * writes past nverts / ntris. */
+NLOSGR_API int nlosgr_mesh_emit(const float* vol, const float* attr, const nlosgr_voxel_grid* grid, float level,
+                     const void* workspace, long long nverts, long long ntris, float* verts_out,
+                     float* normals_out, float* attr_out, int32_t* tris_out, void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

@@ -13,6 +13,7 @@ Layers:
     nlosgr.data            Zaragoza capture format, data_shuffle, whole-volume targets / geometry
     nlosgr.checkpoint      reference-keyed checkpoints loadable with weights_only=True
     nlosgr.voxelize        reconstruction output: Gaussians -> voxel grid, max projections, depth map
+    nlosgr.mesh            surface output: isosurface of a voxelized field as a triangle mesh, PLY export
 """
 from . import _lib  # noqa: F401
 from .geometry import Geometry, build_geometry, relay_wall_grid, volume_box_point  # noqa: F401
@@ -20,4 +21,15 @@ from .model import GaussianParams, features_flat  # noqa: F401
 from .render import RenderConfig, RenderFn, bboxes, render, render_backward, render_forward  # noqa: F401
 
 __all__ = ["Geometry", "build_geometry", "relay_wall_grid", "volume_box_point", "GaussianParams",
-           "features_flat", "RenderConfig", "RenderFn", "render", "render_forward", "render_backward", "bboxes"]
+           "features_flat", "RenderConfig", "RenderFn", "render", "render_forward", "render_backward", "bboxes",
+           "Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply"]
+
+_MESH_NAMES = ("Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply")
+
+
+def __getattr__(name):
+    # nlosgr.mesh is imported on first use, so `python -m nlosgr.mesh` runs it as __main__ only
+    if name in _MESH_NAMES:
+        from . import mesh
+        return getattr(mesh, name)
+    raise AttributeError(f"module 'nlosgr' has no attribute {name!r}")

@@ -64,7 +64,7 @@ class AdamGroup(ctypes.Structure):
 
 ADAM_MAX_GROUPS = 8  # NLOSGR_ADAM_MAX_GROUPS
 MAX_PER_RAY = 256   # NLOSGR_MAX_PER_RAY
-ABI_VERSION = 10    # NLOSGR_ABI_VERSION
+ABI_VERSION = 11    # NLOSGR_ABI_VERSION
 
 # nlosgr_options.flags variant selection (NLOSGR_FLAG_*; A/B timing and parity cross-checks, 0 in production)
 FLAG_FLOAT_DRAIN = 0x100   # forward: fp32 claim drain instead of the fixed-point drain
@@ -83,6 +83,7 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_bboxes", "nlosgr_rays_workspace_bytes", "nlosgr_filter_rays", "nlosgr_rays_fwd",
            "nlosgr_rays_bwd", "nlosgr_rays_analytic", "nlosgr_mse_workspace_bytes", "nlosgr_mse", "nlosgr_adam",
            "nlosgr_carve_votes", "nlosgr_voxel_workspace_bytes", "nlosgr_voxelize", "nlosgr_volume_project",
+           "nlosgr_mesh_workspace_bytes", "nlosgr_mesh_count", "nlosgr_mesh_emit",
            "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
@@ -137,6 +138,13 @@ def load():
     lib.nlosgr_voxelize.restype = ctypes.c_int
     lib.nlosgr_volume_project.argtypes = [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]
     lib.nlosgr_volume_project.restype = ctypes.c_int
+    lib.nlosgr_mesh_workspace_bytes.argtypes = [PVG]
+    lib.nlosgr_mesh_workspace_bytes.restype = ctypes.c_size_t
+    lib.nlosgr_mesh_count.argtypes = [_P, PVG, ctypes.c_float, _P, _P, _P]
+    lib.nlosgr_mesh_count.restype = ctypes.c_int
+    lib.nlosgr_mesh_emit.argtypes = [_P, _P, PVG, ctypes.c_float, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P,
+                                     _P, _P, _P]
+    lib.nlosgr_mesh_emit.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

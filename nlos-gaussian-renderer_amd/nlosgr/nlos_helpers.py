@@ -10,7 +10,8 @@ HIP kernels (no dense [Ng, Na] torch tensors).
     compute_loss                           nlos_helpers.py:280-346     (same loss / equal_loss; no per-step .mat
                                                                         dump unless args.save_loss_mat is set)
     gaussian2volume                        nlos_helpers.py:40-69       (same signature; 'voxel' returns the regular-grid
-                                                                        volumes and projection maps, 'mesh' raises)
+                                                                        volumes and projection maps, 'isosurface' adds
+                                                                        the density's mean-level mesh, 'mesh' raises)
 Without args.use_cuda_renderer the default path T conventions apply (preset "torch"); args.occlusion
 selects the 'netf' self-transmittance model like gaussian_model.py:297-325.  args.render_cutoff
 (optional, default 0 = dense, the reference's exact semantics) enables support culling at that
@@ -182,11 +183,14 @@ def gaussian2volume(args, model, data_kwargs, camera_pos, resolution=128, mode='
     normal y with its depth map, and the same two maps of the density volume (nlosgr.voxelize).  The SH
     albedo is viewed from camera_pos (the reference passes the central wall point, main.py:378-382).
     Conventions follow the rendering path as in gaussian_transient_rendering; args.render_cutoff
-    (default 0 = dense, the reference's semantics) sets the support cutoff.  mode 'mesh' is the
-    reference's open3d Poisson reconstruction (:50-69), which needs open3d: it raises."""
+    (default 0 = dense, the reference's semantics) sets the support cutoff.  mode 'isosurface' returns the
+    same dictionary plus 'mesh' (nlosgr.mesh.Mesh: the density's isosurface at its mean, the reference's
+    threshold :51, albedo interpolated to the vertices) and 'level'.  mode 'mesh' is the reference's open3d
+    Poisson reconstruction (:50-69), which needs open3d: it raises."""
     if mode.lower() == 'mesh':
-        raise NotImplementedError("nlosgr: gaussian2volume(mode='mesh') needs open3d (absent); use mode='voxel'")
-    if mode.lower() != 'voxel':
+        raise NotImplementedError("nlosgr: gaussian2volume(mode='mesh') needs open3d (absent); use mode='isosurface' "
+                                  "(the same threshold, extracted as an isosurface) or mode='voxel'")
+    if mode.lower() not in ('voxel', 'isosurface'):
         raise ValueError(f"nlosgr: unknown gaussian2volume mode {mode!r}")
     from .voxelize import VoxelGrid, front_view, voxelize
     preset = "cuda" if getattr(args, "use_cuda_renderer", False) and CUDA_RENDERER is not None else "torch"
@@ -198,5 +202,10 @@ def gaussian2volume(args, model, data_kwargs, camera_pos, resolution=128, mode='
                          sh_degree=int(model.active_sh_degree))
     front, depth = front_view(alb, grid)
     front_d, depth_d = front_view(dens, grid)
-    return {"density": dens, "albedo": alb, "front": front, "depth": depth, "front_density": front_d,
-            "depth_density": depth_d, "grid": grid}
+    out = {"density": dens, "albedo": alb, "front": front, "depth": depth, "front_density": front_d,
+           "depth_density": depth_d, "grid": grid}
+    if mode.lower() == 'isosurface':
+        from .mesh import isosurface
+        out["level"] = dens.mean().item()
+        out["mesh"] = isosurface(dens, grid, out["level"], values=alb)
+    return out
