@@ -2002,7 +2002,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(NLOSGR_B
                             g0 = fast_exp2(b.c0) * (2.50662827463f * __builtin_amdgcn_sqrtf(sb2));
                             g2 = g0 * sb2;
                         } else {
-                            for (int jb = b.kl; jb < b.kl + b.len; ++jb) {
+                            // A segment the last bin clips (kh = nr - 1) is summed through the end of its last
+                            // round: the rounds have no end mask, so part A holds -P_j a_c w_j for the slots past
+                            // nr - 1 as well (H = 0 there, P_j = E), and on a Gaussian that is still wide there
+                            // only the same slots in part B cancel them in A + E B.  (Past an inner end kh < nr - 1
+                            // those slots hold the Gaussian's tail beyond the cutoff, which is left out as above.)
+                            int jend = b.kl + b.len;
+                            if (jend == nr) {
+                                const int o0 = b.kl & 1;   // the first round starts at the even bin at or below kl
+                                jend = b.kl - o0 + ((b.len + o0 + kRS - 1) / kRS) * kRS;
+                            }
+                            for (int jb = b.kl; jb < jend; ++jb) {
                                 const float kj = b.kap0 + (float)(jb - b.kl);
                                 const float pj = fast_exp2(fmaf(b.c2, kj * kj, b.c0));
                                 g0 += pj;
