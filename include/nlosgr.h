@@ -200,9 +200,10 @@ NLOSGR_API int nlosgr_count_support(const nlosgr_gaussians* g, const nlosgr_geom
 /* Fixed-point forward state after an nlosgr_render_fwd on `workspace` (same g / geo / opt): info_out
  * (DEVICE, [8] int32, overwritten, copied on the stream) = {E: the unit 2^-E of the fixed-point drain,
  * E of the launch's largest amplitude bound, LDS histogram flushes into the u64 row, bright segments
- * (peak >= 2^24 units, added straight into the u64 row), bright Gaussians, twins (two adjacent rays of a
- * pair drained by one lane as one segment), twins split at the merge guard (drained as two segments), the
- * longest twin in bins (NLOSGR_FLAG_FX_TWIN_STATS only)};
+ * (peak >= 2^24 units, added straight into the u64 row), bright Gaussians, groups (two or more adjacent
+ * rays of one row of a pair, drained by one lane as one segment; today a group holds two rays), groups split at
+ * the merge guard (the rays the lane could not keep are drained as single segments), the longest group in bins
+ * (NLOSGR_FLAG_FX_TWIN_STATS only)};
  * all zero when the forward did not take the fixed-point drain.  Diagnostics / tests.  (ABI 10: [8], was [4].) */
 NLOSGR_API int nlosgr_fx_info(const nlosgr_gaussians* g, const nlosgr_geometry* geo, const nlosgr_options* opt,
                    const void* workspace, int32_t* info_out, void* hip_stream);

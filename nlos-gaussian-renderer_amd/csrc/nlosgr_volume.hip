@@ -34,6 +34,7 @@
 #include <stdlib.h>
 
 #include "nlosgr_common.hpp"
+#include "nlosgr_enum.hpp"
 
 using namespace nlosgr;
 using namespace nlosgr::detail;
@@ -79,8 +80,8 @@ struct KArgs {
     unsigned long long* hfx;     // forward FX drain: fixed-point histogram [P][nr] (u64, integer adds)
     int* fx_info;                // forward FX drain: [0] unit exponent E (fx_unit_kernel), [1] E of the launch's
                                  // largest bound, [2] LDS flushes, [3] bright segments, [4] bright Gaussians,
-                                 // [5] twins drained as one segment, [6] twins split (fx_twin_setup), [7] the
-                                 // longest twin in bins (NLOSGR_FLAG_FX_TWIN_STATS)
+                                 // [5] groups of two or more rays drained as one segment, [6] groups split
+                                 // (fx_twin_setup), [7] the longest group in bins (NLOSGR_FLAG_FX_TWIN_STATS)
     const float* fx_bound;       // forward FX drain: amplitude bound per Gaussian [ng] (fx_bound_kernel)
     const int* fx_blist;         // forward FX drain: the bright Gaussians (fx_blist_kernel), [fx_info[4]]
 };
@@ -270,9 +271,12 @@ constexpr int kRQ = 256;
 __device__ __forceinline__ unsigned pack_ray(int slot, int i, int j) {
     return (unsigned)slot | ((unsigned)i << 8) | ((unsigned)j << 20);
 }
-// twin entries (the no-occlusion FX forward, see fx_twin_setup): slots are lanes (< 64), so bit 7 of the slot
-// byte marks an entry that stands for the two adjacent cells (i, j) and (i, j + 1) of one pair
-constexpr unsigned kTwinBit = 0x80u;
+// group entries (the no-occlusion FX forward, see enumerate_runs and fx_twin_setup): slots are lanes (< 64), so
+// bits 6-7 of the slot byte carry the group's length - 1: an entry stands for the adjacent cells (i, j) ..
+// (i, j + length - 1) of one pair
+constexpr int kGroupShift = 6;
+constexpr int kGroupMax = 2;   // rays of one row a lane drains at once (the twin drain)
+static_assert(kGroupMax == 2, "fx_twin_setup and the twin round take pairs (trip_plan itself: groups of 2 or 3)");
 
 // ------------------------------------------------------------------------------------------
 // forward
@@ -293,7 +297,8 @@ constexpr int kSteps = NLOSGR_FSTEPS;     // bins per lane per drain round (the 
 constexpr int kStepsNetf = NLOSGR_FSTEPS_NETF;
 // the twin drain (fx_twin_setup) runs longer rounds: a round costs two sets of exp2 seeds, and its unions are
 // longer than single segments (one GPU, 24 / 28 / 32 bins: fwd 657.6 / 642.2 / 632.5 ms; another, 32 / 36 / 40 /
-// 48 bins: 635.7 / 625.1 / 623.7 / 623.6 ms)
+// 48 bins: 635.7 / 625.1 / 623.7 / 623.6 ms; with run-following pairs, 36 / 40 / 44 bins: 564.5 / 562.0 / 563.0 ms,
+// and on another GPU 36 / 40: 566.3 / 564.6 ms: within 2.5 ms of each other, so 36 stays)
 #ifndef NLOSGR_FSTEPS_TWIN
 #define NLOSGR_FSTEPS_TWIN 36
 #endif
@@ -401,9 +406,7 @@ __device__ __forceinline__ bool drain_setup(const float* A, const float* u0, flo
 // to the ray queue ring at qbase + cnt.  Branch-free body (every lane evaluates a clamped
 // candidate, `more` masks the result), two candidates per trip so their table reads overlap;
 // returns once cnt >= 64 or every lane exhausted its box (cnt < 64 + 2*64 <= kRQ on return).
-// TWIN (forward only): two candidates of one trip that are the adjacent cells (i, j) and (i, j + 1) and both
-// pass become ONE entry flagged kTwinBit (a cell joins at most one twin), so a trip appends at most NC entries.
-template <bool DENSE, bool REC = false, bool TWIN = false>
+template <bool DENSE, bool REC = false>
 __device__ __forceinline__ void enumerate_box(const float* M, int i1, int j0, int j1, bool& more, int& ci, int& cj,
                                               const float2* tth, const float2* tph, int nt1, unsigned* rayq,
                                               int qbase, int& cnt, unsigned long long* rec0 = nullptr,
@@ -444,17 +447,6 @@ __device__ __forceinline__ void enumerate_box(const float* M, int i1, int j0, in
         unsigned es[NC];
 #pragma unroll
         for (int u = 0; u < NC; ++u) es[u] = pack_ray(lane, cis[u], cjs[u]);
-        if (TWIN) {
-            bool covered = false;   // cell u is the second ray of the twin that cell u - 1 opened
-#pragma unroll
-            for (int u = 0; u < NC; ++u) {
-                const bool open = !covered && pass[u] && u + 1 < NC && pass[u + 1 < NC ? u + 1 : u] &&
-                                  cis[u + 1 < NC ? u + 1 : u] == cis[u];
-                pass[u] = pass[u] && !covered;
-                es[u] |= open ? kTwinBit : 0u;
-                covered = open;
-            }
-        }
         {
             const bool wrap = cjs[NC - 1] >= j1;
             cj = wrap ? j0 : cjs[NC - 1] + 1;
@@ -466,6 +458,56 @@ __device__ __forceinline__ void enumerate_box(const float* M, int i1, int j0, in
         for (int u = 0; u < NC; ++u) {
             const unsigned long long m = __builtin_amdgcn_ballot_w64(pass[u]);
             if (pass[u]) rayq[(qbase + at + lanes_below(m)) & (kRQ - 1)] = es[u];
+            at += __popcll(m);
+        }
+        cnt = at;
+    } while (cnt < 64 && __builtin_amdgcn_ballot_w64(more));
+}
+
+// Run-following enumeration (the twin drain of the no-occlusion FX forward; lane = pair).  A trip tests
+// kTripCells consecutive cells of ONE row of the box (one theta read, kTripCells phi reads; cells past the
+// row's end repeat its first cell and are masked) and never wraps, so the passing cells of a row pair up
+// along their run wherever the trips fall: trip_plan (nlosgr_enum.hpp) cuts every run into groups of K from
+// its left end and defers a short group at the trip's right edge to the next trip, which tests those cells
+// again.  One group = one queue entry (pack_ray with length - 1 at kGroupShift).  A trip consumes at least one
+// cell and appends at most kTripGroups entries: cnt < 64 + kTripGroups * 64 <= kRQ on return.
+template <int K>
+__device__ __forceinline__ void enumerate_runs(const float* M, int i1, int j0, int j1, bool& more, int& ci, int& cj,
+                                               const float2* tth, const float2* tph, int nt1, unsigned* rayq,
+                                               int qbase, int& cnt) {
+    static_assert(64 + kTripGroups * 64 <= kRQ, "a trip appends at most kTripGroups entries per lane: 64 queued + "
+                                                "kTripGroups * 64 appended must fit the ray queue ring");
+    const int lane = lane_id();
+    do {
+        // all table reads are issued before any queue store, the tests are unpredicated
+        const int n = min(kTripCells, j1 - cj + 1);   // cells of this trip (>= 1 while more)
+        const float2 th = tth[min(ci, nt1)];
+        float2 phs[kTripCells];
+#pragma unroll
+        for (int u = 0; u < kTripCells; ++u) phs[u] = tph[u < n ? cj + u : cj];
+        unsigned bits = 0u;
+#pragma unroll
+        for (int u = 0; u < kTripCells; ++u)
+            bits |= (more & (u < n) & (quadric(M, th.x * phs[u].x, th.x * phs[u].y, th.y) >= 0.f)) ? 1u << u : 0u;
+        const TripPlan tp = trip_plan(bits, n, cj + kTripCells <= j1, K);
+        unsigned es[kTripGroups];
+        bool put[kTripGroups];
+#pragma unroll
+        for (int g = 0; g < kTripGroups; ++g) {
+            put[g] = more && g < tp.count;
+            es[g] = pack_ray(lane | ((tp.len[g] - 1) << kGroupShift), ci, cj + tp.start[g]);
+        }
+        {
+            const bool wrap = cj + tp.consumed > j1;
+            cj = wrap ? j0 : cj + tp.consumed;
+            ci += wrap ? 1 : 0;
+            more = more & (ci <= i1);
+        }
+        int at = cnt;
+#pragma unroll
+        for (int g = 0; g < kTripGroups; ++g) {
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(put[g]);
+            if (put[g]) rayq[(qbase + at + lanes_below(m)) & (kRQ - 1)] = es[g];
             at += __popcll(m);
         }
         cnt = at;
@@ -820,7 +862,8 @@ __device__ __forceinline__ void tail_round(const Drain& d, const float t, float&
 // Twin drain (TW; the no-occlusion FX forward with the refill deal, the training hot path).  The forward is
 // paced by the number of ds_add_u64 it issues, and that number is set by rays: a lane that drains the two
 // adjacent cells (i, j), (i, j + 1) of one pair at once sums their values in registers and issues one add for
-// both.  The two segments' closest-approach bins are a few bins apart, so their union is little longer than
+// both (the cells are paired along their row's run of passing cells, see enumerate_runs).
+// The two segments' closest-approach bins are a few bins apart, so their union is little longer than
 // either (scripts/twin_estimate.py), and both setups share the pair's shuffled A, u0, lw.
 // The lane walks the union [min kl, max kh]; each ray's recurrence is seeded at the round's first bin from its
 // own (t, ga, al).  Outside its own support a ray adds its exact Gaussian values (< exp(-m_c^2 / 2) of its peak,
@@ -1008,8 +1051,11 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
         while (true) {
             if (qcount < 64 && __builtin_amdgcn_ballot_w64(more)) {
                 wave_sync();
-                enumerate_box<DENSE, CACHE, TW>(P.M, P.i1, P.j0, P.j1, more, ci, cj, tth, tph, nt - 1, rayq, qhead,
-                                            qcount, &crec0, &crec1, &ccell);
+                if (TW)
+                    enumerate_runs<kGroupMax>(P.M, P.i1, P.j0, P.j1, more, ci, cj, tth, tph, nt - 1, rayq, qhead, qcount);
+                else
+                    enumerate_box<DENSE, CACHE>(P.M, P.i1, P.j0, P.j1, more, ci, cj, tth, tph, nt - 1, rayq, qhead,
+                                                qcount, &crec0, &crec1, &ccell);
                 wave_sync();
             }
             const bool anymore = __builtin_amdgcn_ballot_w64(more) != 0;
@@ -1036,7 +1082,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                 int tcode = 0;   // TW: fx_twin_setup's result
                 if (TW) {
                     if (take && !(flags & 1)) {
-                        const bool twin = (e & kTwinBit) != 0u;
+                        const bool twin = ((e >> kGroupShift) & 3u) != 0u;
                         float pk = 0.f;
                         // (j + 1 <= j1 < np for a twin entry; a single reads its own cell twice)
                         tcode = fx_twin_setup(A, u0, lws, tth[i], tph[j], tph[twin ? j + 1 : j], twin, nr, mc2, r0, dr,

@@ -56,8 +56,11 @@ def main(src, tag):
     nsteps = line["steps"] + line["warmup"]
     for f in glob.glob(os.path.join(src, "kt_*kernel_stats.csv")):
         shutil.copy(f, os.path.join(out, f"{tag}_kernel_stats.csv"))
-    fetch = per_kernel(glob.glob(os.path.join(src, "fetch_*counter_collection.csv"))[0])
-    write = per_kernel(glob.glob(os.path.join(src, "write_*counter_collection.csv"))[0])
+    ff = glob.glob(os.path.join(src, "fetch_*counter_collection.csv"))
+    wf = glob.glob(os.path.join(src, "write_*counter_collection.csv"))
+    traffic = bool(ff and wf)   # a run without the two traffic passes (PASSES="kt sq_drain") writes no traffic file
+    fetch = per_kernel(ff[0]) if traffic else {}
+    write = per_kernel(wf[0]) if traffic else {}
     res = {}
     for k in sorted(set(fetch) | set(write)):
         if not ours(k):
@@ -69,16 +72,17 @@ def main(src, tag):
         # per step: the backward runs one bwd_kernel / sh_kernel launch per wall-point batch
         res[short(k)] = {"fetch_bytes_x2": fb, "write_bytes": wb, "hbm_bytes_per_launch": fb + wb,
                          "launches": n, "launches_per_step": n / nsteps, "hbm_bytes_per_step": (fb + wb) * n / nsteps}
-    with open(os.path.join(out, f"{tag}_traffic.json"), "w") as f:
-        json.dump({"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of bench.py ({tag})",
-                   **wl, "kernels": res}, f, indent=1)
+    if traffic:
+        with open(os.path.join(out, f"{tag}_traffic.json"), "w") as f:
+            json.dump({"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of bench.py ({tag})",
+                       **wl, "kernels": res}, f, indent=1)
     # the bench line read the previously committed traffic/VALU profiles when it ran: restate its
     # roofline.traffic from the passes of this same run
     sys.path.insert(0, ROOT)
     from bench import phase_traffic
     tiles = wl["mode"] == "occl" or wl["selection"] == "aabb"
     dom = line["roofline"]["kernel"].split()[1]          # "nlosgr fwd (...)" / "nlosgr bwd (...)"
-    per = {ph: phase_traffic(res, ("tiles_" + ph) if tiles else ph)[0] for ph in ("fwd", "bwd")}
+    per = {ph: phase_traffic(res, ("tiles_" + ph) if tiles else ph)[0] for ph in ("fwd", "bwd")} if traffic else {}
     if per.get(dom) is not None:
         line["roofline"]["traffic"] = per[dom]
         line["roofline"]["traffic_per_phase"] = {"fwd": per["fwd"], "bwd": per["bwd"],

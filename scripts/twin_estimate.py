@@ -1,19 +1,22 @@
-"""CPU replay of the forward's segment geometry: what the twin drain (csrc/nlosgr_volume.hip, fx_twin_setup)
-can save at a benchmark configuration.
+"""CPU replay of the forward's enumeration and segment geometry: what grouping adjacent rays into one lane
+(csrc/nlosgr_volume.hip, enumerate_runs and fx_twin_setup) saves at a benchmark configuration.
 
-For a sample of (wall point, Gaussian) pairs of the seeded C3 scene it evaluates the kernel's own support
-formulas in float64 (ray_setup: closest approach, m2min, [kl, kh]), walks each pair's candidate box in
-row-major trips of NC cells as enumerate_box does, pairs two passing cells (i, j), (i, j + 1) of one trip, and
-reports
-  * rays per pair and bins per segment (to compare with the profile's 26.7 / 66.0 at C3, 5.7 sigma),
-  * the fraction of rays that find a twin, the union length against the two lengths, the distance of the
-    two closest-approach bins,
-  * lane-rounds (= ds_add_u64 instructions / (kSteps / 2)) and segments taken at refills, single vs twin.
+For a sample of (wall point, Gaussian) pairs of the seeded C3 scene it evaluates, in float64, the kernel's own
+bounding-sphere box (pair_setup) and support formulas (ray_setup: closest approach, m2min, [kl, kh]) through
+nlosgr/enum_replay.py, groups each box's passing cells the way the chosen scheme does and reports
+  * rays, box cells and rows per pair, passing cells per row, rows whose passing cells are not contiguous,
+  * cells tested and trips (the enumeration's own work),
+  * queue entries per ray and the share of rays in groups of two or more,
+  * lane-rounds (= ds_add_u64 instructions / (round length / 2)) at the given round length, against the
+    one-ray-per-lane drain at 28-bin rounds.
 
-    python scripts/twin_estimate.py [--nc 3] [--gaussians 300] [--walls 8] [--steps 28]
+    python scripts/twin_estimate.py [--pairing trip|run] [--group 2|3] [--steps 36] [--gaussians 400] [--walls 6]
+
+--pairing trip: row-major trips of 3 cells that wrap across rows, two adjacent passing cells of a trip pair up
+(the scheme before enumerate_runs; --group 2 only).  --pairing run: trips of 4 cells of one row, trip_plan of
+csrc/nlosgr_enum.hpp.
 """
 import argparse
-import math
 import os
 import sys
 
@@ -21,110 +24,74 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "nlos-gaussian-renderer_amd"))
-
-
-def rot(q):
-    r, x, y, z = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)],
-                     [2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x)],
-                     [2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)]])
+sys.path.insert(0, ROOT)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--nc", type=int, default=3, help="candidate cells per enumeration trip")
-    ap.add_argument("--gaussians", type=int, default=300)
-    ap.add_argument("--walls", type=int, default=8)
-    ap.add_argument("--steps", type=int, default=28, help="bins per drain round (NLOSGR_FSTEPS)")
+    ap.add_argument("--pairing", choices=("trip", "run"), default="run")
+    ap.add_argument("--group", type=int, choices=(2, 3), default=2, help="rays per lane at most (K)")
+    ap.add_argument("--gaussians", type=int, default=400)
+    ap.add_argument("--walls", type=int, default=6)
+    ap.add_argument("--steps", type=int, default=36, help="bins per drain round of the grouped drain")
+    ap.add_argument("--single-steps", type=int, default=28, help="bins per round of the one-ray-per-lane drain")
     ap.add_argument("--cutoff", type=float, default=5.7)
     a = ap.parse_args()
+    if a.pairing == "trip" and a.group != 2:
+        ap.error("--pairing trip forms pairs only")
+    from nlosgr import enum_replay as E
     from nlosgr.model import GaussianParams
     from nlosgr.volume import Scene
+    from oracle import torch_ref as R
     ng, H, T, ns = 100000, 128, 1024, 32
     scene = Scene(H=H, W=H, T=T, ns=ns)
     m = GaussianParams.synthetic(ng, 3, preset="cuda", device="cpu", seed=0)
     geo = scene.geometry("cpu", "cuda", "noocl")
     rng = np.random.default_rng(0)
-    gs = rng.choice(ng, a.gaussians, replace=False)
+    gs = np.sort(rng.choice(ng, a.gaussians, replace=False))
     ps = rng.choice(H * H, a.walls, replace=False)
-    mu = m._mu.detach().numpy().astype(np.float64)
-    sc = np.exp(m._scaling.detach().numpy().astype(np.float64))
-    q = m._rotation.detach().numpy().astype(np.float64)
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    r = geo.r.numpy().astype(np.float64)
-    nr = len(r)
-    r0, dr = r[0], (r[-1] - r[0]) / (nr - 1)
-    mc2 = a.cutoff ** 2
-    S = a.steps
+    sub = lambda t: t.detach()[gs]
+    Pm = R.Params(sub(m._mu), sub(m._scaling), sub(m._rotation), sub(m._opacity), sub(m._features_dc),
+                  sub(m._features_rest), int(m.active_sh_degree), requires_grad=False)
+    mu = sub(m._mu).numpy().astype(np.float64)
+    A, smax = E.gaussian_frames(mu, sub(m._scaling).numpy(), sub(m._rotation).numpy())
 
-    def rounds(l0, l1):   # rounds start at the even bin at or below the first bin
-        return math.ceil((l1 - l0 + 1 + (int(l0) & 1)) / S)
-
-    rays = pairs = twinned = 0
-    len_sum = union_sum = twin_len_sum = 0.0
-    rounds_single = rounds_twin = 0
-    dks = []
+    pairs = rays = cells = rows = prow = noncontig = tested = trips = entries = grouped = 0
+    rounds = rounds_single = 0
     for p in ps:
-        st, ct = (geo.sin_theta[p].numpy().astype(np.float64), geo.cos_theta[p].numpy().astype(np.float64))
-        sp, cp = (geo.sin_phi[p].numpy().astype(np.float64), geo.cos_phi[p].numpy().astype(np.float64))
-        D = np.stack([st[:, None] * cp[None, :], st[:, None] * sp[None, :],
-                      np.broadcast_to(ct[:, None], (ns, ns))], axis=-1)
-        w = geo.wall[p].numpy().astype(np.float64)
-        for g in gs:
-            A = np.diag(1 / sc[g]) @ rot(q[g]).T
-            u0 = A @ (w - mu[g])
-            V = D @ A.T
-            av = (V * V).sum(-1)
-            uv = V @ u0
-            ts = -uv / av
-            m2 = (u0 @ u0) - uv * uv / av
-            ks = (ts - r0) / dr
-            hk = np.sqrt(np.maximum(mc2 - m2, 0) / av) / dr
-            kl = np.maximum(np.ceil(ks - hk), 0)
-            kh = np.minimum(np.floor(ks + hk), nr - 1)
-            ok = (m2 <= mc2) & (kl <= kh)
-            if not ok.any():
-                continue
+        box, ok, kl, kh = E.wall_point_cells(geo, int(p), mu, A, smax, a.cutoff)
+        rho = R.albedo(Pm, geo.wall[int(p)].float(), preset="cuda")[:, 0].numpy()
+        ok &= (rho > 0)[:, None, None]
+        for g in np.nonzero(ok.any((1, 2)))[0]:
+            i0, i1, j0, j1 = box[g]
+            okb = ok[g, i0:i1 + 1, j0:j1 + 1]
+            klb, khb = kl[g, i0:i1 + 1, j0:j1 + 1], kh[g, i0:i1 + 1, j0:j1 + 1]
             pairs += 1
-            ii, jj = np.where(ok)   # the candidate box: the passing cells and one row / column of margin
-            i0, i1 = max(ii.min() - 1, 0), min(ii.max() + 1, ns - 1)
-            j0, j1 = max(jj.min() - 1, 0), min(jj.max() + 1, ns - 1)
-            cells = [(i, j) for i in range(i0, i1 + 1) for j in range(j0, j1 + 1)]
-            for c0 in range(0, len(cells), a.nc):
-                trip = cells[c0:c0 + a.nc]
-                u = 0
-                while u < len(trip):
-                    i, j = trip[u]
-                    if not ok[i, j]:
-                        u += 1
-                        continue
-                    rays += 1
-                    L = kh[i, j] - kl[i, j] + 1
-                    len_sum += L
-                    rs = rounds(kl[i, j], kh[i, j])
-                    rounds_single += rs
-                    if u + 1 < len(trip) and trip[u + 1] == (i, j + 1) and ok[i, j + 1]:
-                        rays += 1
-                        L2 = kh[i, j + 1] - kl[i, j + 1] + 1
-                        len_sum += L2
-                        rounds_single += rounds(kl[i, j + 1], kh[i, j + 1])
-                        ul, uh = min(kl[i, j], kl[i, j + 1]), max(kh[i, j], kh[i, j + 1])
-                        twinned += 2
-                        union_sum += uh - ul + 1
-                        twin_len_sum += L + L2
-                        rounds_twin += rounds(ul, uh)
-                        dks.append(abs(ks[i, j] - ks[i, j + 1]))
-                        u += 2
-                    else:
-                        rounds_twin += rs
-                        u += 1
-    print(f"NC {a.nc}: {pairs} pairs, {rays / pairs:.1f} rays per pair, {len_sum / rays:.1f} bins per segment")
-    print(f"twinned rays {twinned / rays:.3f}; union / mean of the two lengths "
-          f"{2 * union_sum / max(twin_len_sum, 1):.3f}; closest-approach bins apart mean {np.mean(dks):.1f} "
-          f"max {np.max(dks):.1f}")
-    print(f"lane-rounds single {rounds_single}, with twins {rounds_twin}: x{rounds_twin / rounds_single:.3f}")
-    print(f"segments taken at refills single {rays}, with twins {rays - twinned // 2}: "
-          f"x{(rays - twinned // 2) / rays:.3f}")
+            rays += int(okb.sum())
+            cells += okb.size
+            live = okb.any(1)
+            rows += int(live.sum())
+            for row in okb[live]:
+                idx = np.nonzero(row)[0]
+                prow += len(idx)
+                noncontig += int(idx[-1] - idx[0] + 1 != len(idx))
+            grp, nt_, ntr = E.groups_trip(okb) if a.pairing == "trip" else E.groups_run(okb, a.group)
+            tested += nt_
+            trips += ntr
+            entries += len(grp)
+            grouped += sum(l for _, _, l in grp if l > 1)
+            rounds += E.lane_rounds(grp, klb, khb, a.steps)
+            singles = [(i, j, 1) for i, j in zip(*np.nonzero(okb))]
+            rounds_single += E.lane_rounds(singles, klb, khb, a.single_steps)
+    print(f"{a.gaussians} Gaussians x {a.walls} wall points: {pairs} pairs, {rays} rays; per pair {rays / pairs:.1f} "
+          f"rays, {cells / pairs:.1f} box cells, {rows / pairs:.1f} rows; {prow / rows:.1f} passing cells per row, "
+          f"{noncontig} rows not contiguous")
+    print(f"pairing {a.pairing}, K {a.group}: cells tested {tested}, trips {trips}; entries per ray "
+          f"{entries / rays:.3f}; rays in groups {grouped / rays:.3f}")
+    at = rounds * a.steps
+    at1 = rounds_single * a.single_steps
+    print(f"lane-rounds at {a.steps} bins {rounds} (one ray per lane at {a.single_steps} bins: {rounds_single}); "
+          f"atomics (lane-rounds x bins per round) vs the one-ray drain x{at / at1:.3f}")
 
 
 if __name__ == "__main__":
