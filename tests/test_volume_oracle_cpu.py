@@ -8,6 +8,13 @@ volume_oracle (e_g <= tol s_g + b_g).  Both bounds are a few times the fp32 orac
 fraction of a bin wide, whose few samples sit on the steep flank of the pdf, where the fp32 rounding of a
 sample's position is amplified by m^2 / 2 ~ 16) has bounds of its own, ten times the general ones: NARROW_TOL per
 Gaussian (measured there <= 2.1e-5) and NARROW_FWD_TOL for the forward (measured 5.0e-6, the same amplification).
+
+The per-bin forward metric (volume_oracle.forward_bins / forward_bin_failures) is pinned in three ways, on the
+scenes tests/test_gpu_fwd_edges.py runs and at their sizes: (a) the fp32 oracle passes it at 2e-5 with no rounding
+allowance, so the tolerance is not below fp32 noise; (b) four synthetic faults of one ray of one Gaussian, planted
+in the float64 reference, are rejected even at the coarsest fixed-point unit the scene allows, while the row-maximum
+figure the earlier forward tests use lets the first two pass; (c) in at least three quarters of the non-empty bins
+neither the dense-culled bracket nor the rounding bound is what decides.
 """
 import pytest
 import torch
@@ -107,3 +114,176 @@ def test_as_named_splits_the_flat_feature_gradient():
     assert [tuple(d[n].shape) for n in VO.NAMES] == [(ng, 3), (ng, 3), (ng, 4), (ng, 1), (ng, 1), (ng, K - 1)]
     assert torch.equal(d["features_dc"][:, 0], five[4][:, 0].double())
     assert torch.equal(d["features_rest"], five[4][:, 1:].double())
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the per-bin forward metric
+# ---------------------------------------------------------------------------------------------------------
+CUT = 5.7
+
+
+def _bins(model, geo, k, preset, mode, cutoff=CUT):
+    P = VO.params_of_model(model)
+    cdt = k["c"] * k["deltaT"]
+    fb = VO.forward_bins(P, geo, preset, mode, cdt, cutoff)
+    return P, cdt, fb
+
+
+@pytest.mark.parametrize("preset", ["torch", "cuda"])
+@pytest.mark.parametrize("mode", ["noocl", "netf"])
+@pytest.mark.parametrize("T,ns", [(41, 6), (97, 6), (97, 8), (257, 8), (0, 6)])
+def test_fp32_oracle_passes_the_per_bin_metric(preset, mode, T, ns):
+    """(a) Scene 1 (T = 0: its compact variant): another fp32 evaluation of the same sums is within 2e-5 of every
+    bin's own scale (Q = 0)."""
+    model, geo, k = VO.parity_scene(preset, mode, T, ns=ns) if T else VO.compact_scene(preset, mode, ns=ns)
+    P, cdt, fb = _bins(model, geo, k, preset, mode)
+    with torch.no_grad():
+        hist = R.render_volume(P, k["walls"], k["box"], k["Y"], k["ns"], k["start"], k["end"], k["c"], k["deltaT"],
+                               preset=preset, mode=mode, mc=CUT)
+    tol = VO.forward_tolerance(P, geo, preset, CUT, base=2e-5)
+    w = VO.forward_bin_worst(hist, fb)
+    print(f"\n{preset} {mode} T={T} ns={ns}: fp32 oracle per bin {w:.2e}, per row "
+          f"{VO.forward_worst(hist, VO.as_row_reference(fb)):.2e}")
+    assert VO.forward_bin_failures(hist, fb, tol) == []
+    assert VO.forward_bin_failures(fb.ref, fb, 0.0) == [] and VO.forward_bin_worst(fb.ref, fb) == 0.0
+
+
+def test_per_bin_metric_rejects_single_ray_faults():
+    """(b) Scene 1, compact (volume_oracle.compact_scene: cuda, noocl, T = 97, ns = 6; about 1700 rays per wall
+    point, rows with structure).  Each fault changes one ray of one Gaussian at wall point 0 in the float64
+    reference: drained one bin late; its last in-support bin dropped; left out; added twice (the ray after it in
+    its row, as a pair whose second ray is drained again).  The bound uses the coarsest unit the quantile rule can
+    pick (coarsest_E) and FWD_BIN_TOL with the position allowance.  The two figures are computed for every
+    (Gaussian, ray), and the example is the ray on which the per-bin metric rejects the first two faults most
+    clearly among those where 2e-5 of the row maximum, the earlier forward tests' figure, passes both: the gap this
+    metric closes.  (On the broad scene 1 the rows are flat, every bin is near its row's maximum, and the two
+    figures reject the same rays.)  Over all rays the per-bin metric at the coarsest unit rejects somewhat fewer
+    planted faults than 2e-5 of the row maximum: its gain is the independent reference and the bins away from the
+    row's peak, not a uniformly sharper rule."""
+    model, geo, k = VO.compact_scene()
+    P, cdt, fb = _bins(model, geo, k, "cuda", "noocl")
+    tol = VO.forward_tolerance(P, geo, "cuda", CUT)
+    E = VO.coarsest_E(P, "cuda", "noocl", cdt)
+    row = VO.as_row_reference(fb)
+    with torch.no_grad():
+        t = VO.ray_terms(VO.Params64(P), VO.tables(geo), 0, "cuda", "noocl", cdt, CUT)      # [Ng, nr, rays]
+    ng, nr, nray = t.shape
+    ta, b, q = VO._bin_bound(fb, tol, E)
+    bound, top = (ta + b + q)[0], fb.ref[0].max()
+    late = torch.zeros_like(t)
+    late[:, 1:] = t[:, :-1]
+    klast = ((t > 0) * torch.arange(nr)[None, :, None]).amax(dim=1, keepdim=True)            # [Ng, 1, rays]
+    last = torch.zeros_like(t).scatter_(1, klast, t.gather(1, klast))
+    deltas = {"one bin late": late - t, "last bin dropped": -last, "left out": -t,
+              "second ray of a pair twice": torch.roll(t, -1, dims=2)}
+    hit = (t > 0).any(dim=1)
+    figs = {}
+    for name, d in deltas.items():
+        figs[name] = ((d.abs() / bound[None, :, None]).amax(dim=1), d.abs().amax(dim=1) / top)   # [Ng, rays] each
+        print(f"\n{name}: of the {int(hit.sum())} (Gaussian, ray) in support the per-bin metric rejects "
+              f"{int((figs[name][0] > 1)[hit].sum())}, 2e-5 of the row maximum "
+              f"{int((figs[name][1] > 2e-5)[hit].sum())}, "
+              f"the per-bin metric alone {int(((figs[name][0] > 1) & (figs[name][1] <= 2e-5))[hit].sum())}")
+    # floors, so that the scene cannot drift into one where the metric sees little: at the coarsest unit it rejects
+    # more than half of the rays drained a bin late and two thirds of the rays left out (measured 787 and 1024 of
+    # 1511; 2e-5 of the row maximum 886 and 1142), and some of each fault that the row figure passes
+    nhit = int(hit.sum())
+    assert int((figs["one bin late"][0] > 1)[hit].sum()) > 0.5 * nhit
+    assert int((figs["left out"][0] > 1)[hit].sum()) > 0.65 * nhit
+    assert all(int(((f[0] > 1) & (f[1] <= 2e-5))[hit].sum()) > 0 for f in figs.values())
+    f1, f2 = figs["one bin late"], figs["last bin dropped"]
+    ok = hit & (f1[1] <= 2e-5) & (f2[1] <= 2e-5) & (torch.arange(nray) % geo.np < geo.np - 1)[None, :]
+    score = torch.where(ok, torch.minimum(f1[0], f2[0]), torch.zeros_like(f1[0]))
+    g, ray = divmod(int(score.argmax()), nray)
+    passed_by_row = []
+    for name, d in deltas.items():
+        faulty = fb.ref.clone()
+        faulty[0] += d[g, :, ray]
+        bad = VO.forward_bin_failures(faulty, fb, tol, E)
+        rw, bw = VO.forward_worst(faulty, row), VO.forward_bin_worst(faulty, fb, E)
+        print(f"Gaussian {g} ray {ray}, {name}: {rw:.2e} of the row maximum (the old figure), {bw:.2e} of the bin's "
+              f"own scale beyond B + Q (tolerance {float(tol[g]):.2e}); {len(bad)} bins fail")
+        assert bad and all(f[0] == 0 for f in bad), name
+        passed_by_row.append(rw <= 2e-5)
+    assert passed_by_row[0] and passed_by_row[1], passed_by_row
+    assert VO.forward_bin_failures(fb.ref, fb, tol, E) == []
+
+
+def _coverage_scenes():
+    """(name, (model, geo, consts), preset, mode, held): every scene family of tests/test_gpu_fwd_edges.py, built by
+    that file's own builders; held = False for the exempt ones."""
+    import test_gpu_fwd_edges as FE
+    yield "1 cuda noocl T=97", VO.parity_scene("cuda", "noocl", 97), "cuda", "noocl", True
+    yield "1 torch netf T=257", VO.parity_scene("torch", "netf", 257, ns=8), "torch", "netf", True
+    yield "1 cuda netf T=97 ns=8", VO.parity_scene("cuda", "netf", 97, ns=8), "cuda", "netf", True
+    yield "1 compact noocl", VO.compact_scene(), "cuda", "noocl", True
+    yield "1 compact netf", VO.compact_scene(mode="netf"), "cuda", "netf", True
+    for L in (19, 36, 72):
+        model, geos, k = FE._one_gaussian(L, "noocl", 40)
+        yield f"2 one Gaussian L={L}", (model, geos[0], k), "cuda", "noocl", False
+    for T in (7, 17, 35):
+        yield f"3 short rows T={T}", FE._short_row_scene(T, "noocl", None)[:3], "cuda", "noocl", True
+    for ns in (5, 16):
+        yield f"4 runs ns={ns}", VO.runs_scene(ns), "cuda", "noocl", True
+    for ng in (1, 2, 65, 257, 2049):
+        yield f"5 lanes ng={ng}", VO.lanes_scene(ng, 3), "cuda", "noocl", True
+    yield "5 lanes ng=513 netf", VO.lanes_scene(513, 5, mode="netf"), "cuda", "netf", True
+    yield "6 needles", FE._needle_scene("noocl", None), "cuda", "noocl", False
+    for mode in ("noocl", "netf"):
+        yield f"6 thin axis {mode}", FE._thin_scene(mode, None), "cuda", mode, True
+        yield f"6 sub-bin {mode}", FE._sub_bin_scene(mode, None), "cuda", mode, True
+    for nb in (0, 1, 2, 3, 30):
+        yield f"7 bright {nb}", VO.bright_scene(nb), "cuda", "noocl", nb <= 1
+    yield "7 flush pile", VO.pile_scene(), "cuda", "noocl", True
+
+
+def test_bracket_and_rounding_do_not_decide_most_bins():
+    """(c) Per scene, of the bins with ref > 0 at most a quarter have B + Q > 10 sum_g tol_g (A_g + B_g).  E is the
+    coarsest the scene allows, except for scene 7, whose point is the unit the quantile rule picks (quantile_E; the
+    GPU test asserts the kernel's E equals it).  Every scene family of tests/test_gpu_fwd_edges.py is printed; held
+    to the quarter are all but three, which are exempt for the reason given and listed with their measured fraction:
+      scene 2 (0.22 to 0.32)  one Gaussian alone: the bins at its own edge hold only samples beyond 4 sigma
+      6 needles (0.26)        each crossing is a single ray's profile; its flank bins are below the rounding bound
+                              of the wall point's hundred rays (0.24 to 0.34 for other placements of the needles)
+      7 bright 2, 3, 30       (0.73, 0.66, 0.56) the unit is coarsened on purpose: Q is what the case is about
+    Scene 6 (thin axis, sub-bin) and the pile meet it with equally bright Gaussians of a tight amplitude bound
+    (volume_oracle.tight_albedo) and, for the pile, a row cut to its core."""
+    worst = 0.0
+    for name, (model, geo, k), preset, mode, held in _coverage_scenes():
+        P, cdt, fb = _bins(model, geo, k, preset, mode)
+        E = VO.quantile_E(P, preset, mode, cdt, geo.nt * geo.np)[0] if name.startswith("7 bright") \
+            else VO.coarsest_E(P, preset, mode, cdt)
+        c = VO.forward_bin_coverage(fb, VO.forward_tolerance(P, geo, preset, CUT), E)
+        print(f"\n{name}: E {E:.2f}, {int((fb.ref > 0).sum())} of {fb.ref.numel()} bins live, bracket or rounding "
+              f"decides in {c:.3f} of them" + ("" if held else "  (exempt)"))
+        if held:
+            worst = max(worst, c)
+    assert worst <= 0.25
+
+
+@pytest.mark.parametrize("ng", [1, 2, 63, 64, 65, 255, 256, 257, 513, 2049])
+def test_lanes_scene_every_gaussian_stands_out(ng):
+    """Scene 5: a Gaussian lost at a chunk or split boundary fails a bin outright: every Gaussian (above 65: every
+    one at a chunk boundary, the others are dimmed) has a bin in which its A_g is more than ten times the bin's
+    whole bound, at the coarsest unit."""
+    model, geo, k = VO.lanes_scene(ng, 3)
+    P, cdt, fb = _bins(model, geo, k, "cuda", "noocl")
+    ta, b, q = VO._bin_bound(fb, VO.forward_tolerance(P, geo, "cuda", CUT), VO.coarsest_E(P, "cuda", "noocl", cdt))
+    stand = (fb.A_g / (ta + b + q).clamp_min(1e-300)[:, None, :]).amax(dim=(0, 2))
+    share = (fb.A_g / fb.A.clamp_min(1e-300)[:, None, :]).amax(dim=(0, 2))
+    sel = VO.lane_boundary(ng) if ng > 65 else torch.ones(ng, dtype=torch.bool)
+    print(f"\nng={ng}: {int(sel.sum())} Gaussians checked, least A_g / bound {float(stand[sel].min()):.1f}, least best "
+          f"share of a bin {float(share[sel].min()):.3f}")
+    assert float(stand[sel].min()) > 10.0
+
+
+def test_quantile_rule_of_the_bright_scene():
+    """Scene 7: 300 Gaussians, so the second brightest bound sets the unit: one bright Gaussian leaves it alone
+    (the bright launch carries it), two or more coarsen it to the unit of the bright bounds (7 binary orders)."""
+    E = {}
+    for nb in (0, 1, 2, 3, 30):
+        model, geo, k = VO.bright_scene(nb)
+        E[nb] = VO.quantile_E(VO.params_of_model(model), "cuda", "noocl", k["c"] * k["deltaT"], geo.nt * geo.np)
+    print("\n(E, E of the largest bound) per number of bright Gaussians:", E)
+    assert E[1][0] == E[0][0] and E[1][1] <= E[1][0] - 6
+    assert all(E[nb][0] == E[nb][1] == E[1][1] for nb in (2, 3, 30))
