@@ -18,6 +18,8 @@
  *   nlosgr_rays_analytic <- _C.render_rays_analytic  src/volume_renderer_analytic.cu:178-241
  *   nlosgr_mse / nlosgr_adam <- compute_loss nlos_helpers.py:323-327 + model.optimizer.step()
  *                          main.py:203-213 (torch.optim.Adam groups, gaussian_model.py:223-242)
+ *   nlosgr_irf_apply / nlosgr_mse_irf: no counterpart (the reference trains on synthetic transients only);
+ *                          the detector's temporal response between the render and a measured capture
  *   nlosgr_bboxes       <- compute_gaussian_bboxes_kernel include/bbox_compute.cuh:76-120,
  *                          GaussianModel.get_bboxes gaussian_model/gaussian_model.py:140-178
  *   nlosgr_carve_votes  <- the voting loop of space_carving gaussian_model/gaussian_utils.py:88-99
@@ -44,7 +46,7 @@
 extern "C" {
 #endif
 
-#define NLOSGR_ABI_VERSION 11
+#define NLOSGR_ABI_VERSION 12
 
 /* convention presets */
 enum {
@@ -287,6 +289,48 @@ typedef struct {
 NLOSGR_API size_t nlosgr_mse_workspace_bytes(void);
 NLOSGR_API int nlosgr_mse(const float* hist, const float* target, float gt_times, long long n,
                float grad_scale, float* grad_out, void* workspace, float* loss_out, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Temporal instrument response (ABI 12): a measured transient is the ideal one convolved in time with
+ * the system's impulse response (laser pulse (*) detector jitter, often with a diffusion tail) on a
+ * constant floor of dark counts and ambient light.  Rows are wall points, the time axis is contiguous
+ * ([rows, nr], the layout of hist).  An IRF is ntaps real taps w, a centre c (0 <= c < ntaps) and a
+ * background b:
+ *   apply:    y[p,t] = b + sum_{j<ntaps} w[j] h[p, t + c - j]      (h = 0 outside [0, nr))
+ *   adjoint:  g[p,s] =     sum_{j<ntaps} w[j] z[p, s - c + j]      (z = 0 outside [0, nr))
+ * c = 0 is a causal response, c = argmax w keeps a peak where it was; ntaps = 1, w = {1}, c = 0, b = 0 is
+ * the identity.  Taps may be negative and are not normalised.  Light from before the rendered window
+ * counts as zero: a caller who needs the response of earlier bins widens the window by ntaps bins.
+ * Each sum is a sequential fp32 fma chain over the taps (apply: ascending j, adjoint: descending j)
+ * started at 0, the background added last; no atomics: results are bitwise repeatable and do not depend
+ * on how rows are scheduled.  The taps stay on the device (the host validates sizes and pointers only).
+ * nr > NLOSGR_IRF_MAX_NR: NLOSGR_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------- */
+#define NLOSGR_IRF_MAX_TAPS 512
+#define NLOSGR_IRF_MAX_NR 8192   /* the cap on samples per ray */
+
+typedef struct nlosgr_irf {
+    int32_t ntaps, center;
+    const float* taps;        /* DEVICE [ntaps] */
+    float background;
+} nlosgr_irf;
+
+/* y_out [rows, nr] = apply (adjoint == 0; background added) or adjoint (adjoint != 0; no background) of
+ * x [rows, nr].  y_out must not alias x.  rows == 0 is valid (nothing is launched). */
+NLOSGR_API int nlosgr_irf_apply(const float* x, long long rows, int32_t nr, const nlosgr_irf* irf, int32_t adjoint,
+                     float* y_out, void* hip_stream);
+
+/* nlosgr_mse with y = apply(hist) in place of hist, n = rows * nr:  d = y - gt_times * target,
+ * loss_out[4] = {mean d^2, that / mean (gt*target)^2, sum d^2, sum (gt*target)^2},
+ * grad_out [rows, nr] (may be NULL) = adjoint(grad_scale * 2 d / n) = dL/dhist, which nlosgr_render_bwd
+ * takes unchanged.  One pass: hist and target are read once, grad_out is written once.  The loss sums
+ * are per-row fp32 partials (fixed tree) in the workspace, added in double in row order (256 consecutive
+ * row blocks, then the blocks in order).  workspace: nlosgr_mse_irf_workspace_bytes(rows) bytes.
+ * rows == 0 is valid: loss_out is zeros, as nlosgr_mse gives for n == 0. */
+NLOSGR_API size_t nlosgr_mse_irf_workspace_bytes(long long rows);
+NLOSGR_API int nlosgr_mse_irf(const float* hist, const float* target, float gt_times, long long rows, int32_t nr,
+                   const nlosgr_irf* irf, float grad_scale, float* grad_out, void* workspace, float* loss_out,
+                   void* hip_stream);
 
 /* One torch.optim.Adam step (no weight decay, no amsgrad) over 1..NLOSGR_ADAM_MAX_GROUPS parameter
  * groups; `step` >= 1 is the step count including this update (bias correction).  The scalars are

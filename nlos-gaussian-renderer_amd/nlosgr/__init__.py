@@ -14,6 +14,7 @@ Layers:
     nlosgr.checkpoint      reference-keyed checkpoints loadable with weights_only=True
     nlosgr.voxelize        reconstruction output: Gaussians -> voxel grid, max projections, depth map
     nlosgr.mesh            surface output: isosurface of a voxelized field as a triangle mesh, PLY export
+    nlosgr.irf             temporal instrument response: IRF, gaussian_irf, convolve_time (render -> capture)
 """
 from . import _lib  # noqa: F401
 from .geometry import Geometry, build_geometry, relay_wall_grid, volume_box_point  # noqa: F401

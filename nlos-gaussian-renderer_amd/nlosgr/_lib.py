@@ -62,9 +62,15 @@ class AdamGroup(ctypes.Structure):
                 ("lr", ctypes.c_double)]
 
 
+class Irf(ctypes.Structure):
+    _fields_ = [("ntaps", ctypes.c_int32), ("center", ctypes.c_int32), ("taps", _P), ("background", ctypes.c_float)]
+
+
 ADAM_MAX_GROUPS = 8  # NLOSGR_ADAM_MAX_GROUPS
 MAX_PER_RAY = 256   # NLOSGR_MAX_PER_RAY
-ABI_VERSION = 11    # NLOSGR_ABI_VERSION
+IRF_MAX_TAPS = 512  # NLOSGR_IRF_MAX_TAPS
+IRF_MAX_NR = 8192   # NLOSGR_IRF_MAX_NR
+ABI_VERSION = 12    # NLOSGR_ABI_VERSION
 
 # nlosgr_options.flags variant selection (NLOSGR_FLAG_*; A/B timing and parity cross-checks, 0 in production)
 FLAG_FLOAT_DRAIN = 0x100   # forward: fp32 claim drain instead of the fixed-point drain
@@ -82,6 +88,7 @@ FLAG_FX_TWIN_STATS = 0x20000  # twin drain: record the longest twin in fx_info (
 EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "nlosgr_count_support", "nlosgr_fx_info",
            "nlosgr_bboxes", "nlosgr_rays_workspace_bytes", "nlosgr_filter_rays", "nlosgr_rays_fwd",
            "nlosgr_rays_bwd", "nlosgr_rays_analytic", "nlosgr_mse_workspace_bytes", "nlosgr_mse", "nlosgr_adam",
+           "nlosgr_irf_apply", "nlosgr_mse_irf_workspace_bytes", "nlosgr_mse_irf",
            "nlosgr_carve_votes", "nlosgr_voxel_workspace_bytes", "nlosgr_voxelize", "nlosgr_volume_project",
            "nlosgr_mesh_workspace_bytes", "nlosgr_mesh_count", "nlosgr_mesh_emit",
            "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
@@ -126,6 +133,14 @@ def load():
     lib.nlosgr_mse_workspace_bytes.restype = ctypes.c_size_t
     lib.nlosgr_mse.argtypes = [_P, _P, ctypes.c_float, ctypes.c_longlong, ctypes.c_float, _P, _P, _P, _P]
     lib.nlosgr_mse.restype = ctypes.c_int
+    PIRF = ctypes.POINTER(Irf)
+    lib.nlosgr_irf_apply.argtypes = [_P, ctypes.c_longlong, ctypes.c_int32, PIRF, ctypes.c_int32, _P, _P]
+    lib.nlosgr_irf_apply.restype = ctypes.c_int
+    lib.nlosgr_mse_irf_workspace_bytes.argtypes = [ctypes.c_longlong]
+    lib.nlosgr_mse_irf_workspace_bytes.restype = ctypes.c_size_t
+    lib.nlosgr_mse_irf.argtypes = [_P, _P, ctypes.c_float, ctypes.c_longlong, ctypes.c_int32, PIRF, ctypes.c_float,
+                                   _P, _P, _P, _P]
+    lib.nlosgr_mse_irf.restype = ctypes.c_int
     lib.nlosgr_adam.argtypes = [ctypes.POINTER(AdamGroup), ctypes.c_int32, ctypes.c_longlong, ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, _P]
     lib.nlosgr_adam.restype = ctypes.c_int

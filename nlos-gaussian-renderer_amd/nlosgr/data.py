@@ -46,12 +46,34 @@ def load_zaragoza(path):
             float(flat("c")[0]))
 
 
+def load_irf(path):
+    """The capture's temporal response (nlosgr.irf.IRF) from the optional fields `irf` [L], `irfCenter`
+    and `background` of the file, or None when it has no `irf` field (an ideal detector).  A missing
+    `irfCenter` is the taps' argmax, a missing `background` is 0."""
+    import scipy.io
+    from .irf import IRF
+    m = scipy.io.loadmat(path, variable_names=("irf", "irfCenter", "background"))
+    if "irf" not in m:
+        return None
+    taps = np.asarray(m["irf"], dtype=np.float64).reshape(-1)
+    center = int(np.asarray(m["irfCenter"]).reshape(-1)[0]) if "irfCenter" in m else None
+    background = float(np.asarray(m["background"]).reshape(-1)[0]) if "background" in m else 0.0
+    return IRF(taps, center, background)
+
+
 def save_zaragoza(path, nlos_data, camera_grid_positions, volume_position, volume_size, deltaT, c,
-                  camera_position=(0.0, 0.0, 0.0), camera_grid_size=None, camera_grid_points=None):
-    """Write a capture (or a rendered volume) in the same format load_zaragoza reads."""
+                  camera_position=(0.0, 0.0, 0.0), camera_grid_size=None, camera_grid_points=None, irf=None):
+    """Write a capture (or a rendered volume) in the same format load_zaragoza reads; irf (nlosgr.irf.IRF)
+    adds the optional fields load_irf reads."""
     import scipy.io
     T, H, W = nlos_data.shape
+    extra = {}
+    if irf is not None:
+        extra = {"irf": irf.taps.detach().cpu().numpy().astype(np.float32).reshape(1, -1),
+                 "irfCenter": np.asarray([[irf.center]], dtype=np.int32),
+                 "background": np.asarray([[irf.background]], dtype=np.float64)}
     scipy.io.savemat(path, {
+        **extra,
         "data": np.asarray(nlos_data, dtype=np.float32),
         "cameraPosition": np.asarray(camera_position, dtype=np.float64).reshape(1, 3),
         "cameraGridSize": np.asarray(camera_grid_size if camera_grid_size is not None else (1.0, 1.0)).reshape(1, 2),
@@ -101,6 +123,9 @@ def make_data_kwargs(path, device, shuffle=True):
         "pmin": torch.tensor(pmin, dtype=torch.float, device=device),
         "pmax": torch.tensor(pmax, dtype=torch.float, device=device),
     }
+    irf = load_irf(path)
+    if irf is not None:   # the capture's temporal response: compute_loss and TrainStep(irf=...) apply it
+        data_kwargs["irf"] = irf.to(device)
     return data_kwargs, nlos_data, grid_pos_t, index
 
 

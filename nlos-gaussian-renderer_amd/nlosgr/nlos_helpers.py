@@ -165,6 +165,10 @@ def compute_loss(args, model, data_kwargs, optim_kwargs, device=None):
     with torch.no_grad():
         input_points, I1, I2, num_r, dth, dph, *_ = spherical_sample_histogram(args, data_kwargs, cam)
     result, pred = gaussian_transient_rendering(args, model, data_kwargs, input_points, cam, I1, I2, num_r, dth, dph)
+    if data_kwargs.get("irf") is not None:
+        # the capture's temporal response (nlosgr.irf): the prediction passes through it before the criterion
+        from .irf import convolve_time
+        pred = convolve_time(pred, data_kwargs["irf"])
     with torch.no_grad():
         target = data_kwargs["nlos_data"][I1:(I1 + num_r), m, n] * args.gt_times
     loss = optim_kwargs["criterion"](pred, target)

@@ -8,11 +8,13 @@ iteration for a whole volume (or this rank's band of it) with every piece on the
 host synchronisation inside the step:
 
     render_forward (HIP, records the ray cache)  ->  nlosgr_mse (loss, equal_loss, dL/dhist)
+                                                     [nlosgr_mse_irf when the capture has an IRF]
     ->  render_backward (HIP, walks the ray cache)  ->  [one packed all-reduce when sharded]
     ->  nlosgr_adam (all six groups in one launch; position lr from get_expon_lr_func)
 
 The returned loss is a device tensor; reading it is the caller's choice (and its only sync).
 """
+import ctypes
 import math
 import os
 from dataclasses import dataclass, replace
@@ -61,19 +63,33 @@ class OptimizationParams:
     opacity_reg: float = 0.01
 
 
-def mse(hist, target, gt_times=1.0, grad_scale=1.0, want_grad=True, raw=False):
+def mse(hist, target, gt_times=1.0, grad_scale=1.0, want_grad=True, raw=False, irf=None):
     """(loss2, grad): loss2 = device [2] = (MSE, equal_loss) of compute_loss
     (nlos_helpers.py:323-327) against gt_times * target; grad = grad_scale * dMSE/dhist.
-    raw=True returns the device [4] (MSE, equal_loss, sum d^2, sum (gt target)^2)."""
+    raw=True returns the device [4] (MSE, equal_loss, sum d^2, sum (gt target)^2).
+    irf (nlosgr.irf.IRF): the loss compares the target with the IRF applied to hist along its last
+    axis, and grad is still dL/dhist (nlosgr_mse_irf); None is nlosgr_mse, unchanged."""
     lib = _lib.load()
     dev = hist.device
     h = hist.detach().contiguous()
     t = target.detach().contiguous()
     if h.shape != t.shape or h.dtype != torch.float32 or t.dtype != torch.float32:
         raise ValueError("nlosgr: hist and target must be float32 tensors of one shape")
-    ws = torch.empty(lib.nlosgr_mse_workspace_bytes() // 4, dtype=torch.float32, device=dev)
     out = torch.empty(4, dtype=torch.float32, device=dev)
     grad = torch.empty_like(h) if want_grad else None
+    if irf is not None:
+        if h.dim() < 1:
+            raise ValueError("nlosgr: an IRF needs a time axis")
+        nr = h.shape[-1]
+        rows = h.numel() // nr if nr else 0
+        irf = irf.to(dev)
+        s = irf.struct()
+        ws = torch.empty(lib.nlosgr_mse_irf_workspace_bytes(rows) // 4, dtype=torch.float32, device=dev)
+        _lib.check(lib.nlosgr_mse_irf(_lib.ptr(h), _lib.ptr(t), float(gt_times), rows, nr, ctypes.byref(s),
+                                      float(grad_scale), _lib.ptr(grad), _lib.ptr(ws), _lib.ptr(out),
+                                      _lib.stream_handle(dev)))
+        return (out if raw else out[:2]), grad
+    ws = torch.empty(lib.nlosgr_mse_workspace_bytes() // 4, dtype=torch.float32, device=dev)
     _lib.check(lib.nlosgr_mse(_lib.ptr(h), _lib.ptr(t), float(gt_times), h.numel(), float(grad_scale),
                               _lib.ptr(grad), _lib.ptr(ws), _lib.ptr(out), _lib.stream_handle(dev)))
     return (out if raw else out[:2]), grad
@@ -233,14 +249,20 @@ class TrainStep:
     geo     : nlosgr Geometry of the wall points this process renders (the whole wall, or this
               rank's band from nlosgr.distributed.wall_band).
     target  : [P, T] measured histograms of those wall points (before gt_times).
+    irf     : nlosgr.irf.IRF of the capture (None: an ideal detector, nlosgr_mse as before).  Rows are
+              wall points, so a band or a batch of them needs nothing special.  With keep_grads,
+              self.hist stays the render before the IRF and self.grad_hist is dL/dhist.
     nwall_total : wall points of the whole volume (the MSE is normalised over the whole volume and
               the band gradients / losses are summed over ranks).
     """
 
     def __init__(self, model, geo, cfg, target, gt_times=1.0, opt=None, spatial_lr_scale=1.0, nwall_total=None,
                  group=None, sh_schedule=False, events=None, buckets=4, keep_grads=False, bwd_order="slab",
-                 fwd_order="slab"):
+                 fwd_order="slab", irf=None):
         self.model, self.geo, self.cfg = model, geo, cfg
+        # the capture's temporal response (nlosgr.irf.IRF): every loss of the step compares the target with
+        # the IRF applied to the render; a property of the capture, so checkpoints do not store it
+        self.irf = irf.to(model._mu.device) if irf is not None else None
         # backward / forward Gaussian orders (slab_order; None = as stored)
         self.bwd_order = bwd_order
         self.fwd_order = fwd_order
@@ -360,7 +382,8 @@ class TrainStep:
             if evs:
                 evs[1].record(stream)
             n_b = geo.nwall * geo.nr
-            loss4, grad = mse(hist, self.target[p0:p1], self.gt_times, grad_scale=n_b / self.n_total, raw=True)
+            loss4, grad = mse(hist, self.target[p0:p1], self.gt_times, grad_scale=n_b / self.n_total, raw=True,
+                              irf=self.irf)
             sums += loss4[2:4]
             if evs:
                 evs[2].record(stream)
@@ -408,7 +431,8 @@ class TrainStep:
         if ev:
             ev["fwd"][1].record(stream)
         hist, ws = out[0], (out[2] if cache else None)
-        loss4, grad = mse(hist, self.target, self.gt_times, grad_scale=self.n_local / self.n_total, raw=True)
+        loss4, grad = mse(hist, self.target, self.gt_times, grad_scale=self.n_local / self.n_total, raw=True,
+                          irf=self.irf)
         loss2 = loss4[:2]
         if self.keep_grads:
             self.hist, self.grad_hist = hist, grad
