@@ -29,6 +29,9 @@
  *   nlosgr_mesh_*       <- gaussian2volume(mode='mesh') nlos_helpers.py:50-69: the surface of the density at
  *                          its mean (:51), as an isosurface (marching tetrahedra) in place of the open3d
  *                          Poisson reconstruction
+ *   nlosgr_backproject  no counterpart (the reference has no reconstruction from the capture itself): the
+ *                          back-projection of the measured histograms onto the voxel grid, the baseline
+ *                          reconstruction and a data-driven initial density
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -46,7 +49,7 @@
 extern "C" {
 #endif
 
-#define NLOSGR_ABI_VERSION 12
+#define NLOSGR_ABI_VERSION 13
 
 /* convention presets */
 enum {
@@ -441,6 +444,41 @@ NLOSGR_API int nlosgr_mesh_count(const float* vol, const nlosgr_voxel_grid* grid
 NLOSGR_API int nlosgr_mesh_emit(const float* vol, const float* attr, const nlosgr_voxel_grid* grid, float level,
                      const void* workspace, long long nverts, long long ntris, float* verts_out,
                      float* normals_out, float* attr_out, int32_t* tris_out, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Back-projection of a confocal capture (ABI 13): the voxel-wise sum of each wall point's histogram at the
+ * voxel's time of flight.  rows is [nwall][nr] (the layout data.volume_target returns), walls is [nwall][3],
+ * out is [nx,ny,nz] in nlosgr_voxel_grid order; all device fp32.
+ * For voxel centre x, taken from the grid's tables, and wall point i:
+ *   d = sqrt((dx*dx + dy*dy) + dz*dz), in fp32 and in this order, with no contraction, as carve_kernel forms it.
+ *   u = (d - r0) * inv_dr, k = floor(u), f = u - k.
+ *   s_i = (1-f) h_i[k] + f h_i[k+1], with h_i[j] = 0 for j < 0 or j >= nr.
+ *     s_i is continuous in d everywhere, including at both ends of the window.
+ *     It is zero for u <= -1 or u >= nr.
+ *   out(x) = sum_i d^power s_i.
+ * Summation order is fixed and has no atomics: wall points are taken in ascending order, in tiles of 256
+ * counted from this call's wall point 0; each tile is summed term by term in fp32; the tile sums are added
+ * into a per-voxel fp64 register accumulator, which is rounded to fp32 once at the end.  The result is
+ * bitwise repeatable and independent of how the grid is cut into workgroups: a sub-grid with the same table
+ * values gives the same numbers.  The square root is the hardware one (1 ulp), d^2 = d*d, d^3 = d^2*d,
+ * d^4 = d^2*d^2.
+ * accumulate = 1 adds the call's rounded sum to out: one more rounding per call.  It exists so a wall can be
+ * back-projected in batches or per rank, and is close to, not bitwise equal to, one call over the whole wall.
+ * Non-finite histogram values propagate to the voxels that sample them (0 * NaN included).  nwall == 0
+ * zero-fills out, or leaves it untouched with accumulate.  No workspace.
+ * ------------------------------------------------------------------------------------- */
+typedef struct nlosgr_backproject_opts {
+    float   r0;          /* radius of bin 0 of the rows (I1 * c * deltaT) */
+    float   inv_dr;      /* 1 / (c * deltaT), the caller's fp32 value */
+    int32_t power;       /* weight d^power, 0..4 (falloff compensation) */
+    int32_t accumulate;  /* 0: overwrite out; 1: add this call's sum to out */
+} nlosgr_backproject_opts;
+
+/* Validated on the host (NLOSGR_E_INVALID): extents 1..1024, nr >= 1, nwall >= 0, power 0..4, inv_dr finite and
+ * > 0, r0 finite, null pointers (rows / walls may be NULL only when nwall == 0). */
+NLOSGR_API int nlosgr_backproject(const float* rows, const float* walls, int32_t nwall, int32_t nr,
+                       const nlosgr_voxel_grid* grid, const nlosgr_backproject_opts* opt,
+                       float* out, void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

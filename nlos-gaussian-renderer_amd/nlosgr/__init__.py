@@ -14,6 +14,7 @@ Layers:
     nlosgr.checkpoint      reference-keyed checkpoints loadable with weights_only=True
     nlosgr.voxelize        reconstruction output: Gaussians -> voxel grid, max projections, depth map
     nlosgr.mesh            surface output: isosurface of a voxelized field as a triangle mesh, PLY export
+    nlosgr.backproject     the capture on a voxel grid: back-projection, time filters, backproject_capture
     nlosgr.irf             temporal instrument response: IRF, gaussian_irf, convolve_time (render -> capture)
 """
 from . import _lib  # noqa: F401
@@ -23,8 +24,10 @@ from .render import RenderConfig, RenderFn, bboxes, render, render_backward, ren
 
 __all__ = ["Geometry", "build_geometry", "relay_wall_grid", "volume_box_point", "GaussianParams",
            "features_flat", "RenderConfig", "RenderFn", "render", "render_forward", "render_backward", "bboxes",
-           "Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply"]
+           "Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply",
+           "backproject_capture", "time_filter"]
 
+_BP_NAMES = ("backproject_capture", "time_filter")
 _MESH_NAMES = ("Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply")
 
 
@@ -33,4 +36,9 @@ def __getattr__(name):
     if name in _MESH_NAMES:
         from . import mesh
         return getattr(mesh, name)
+    # the same for `python -m nlosgr.backproject` (nlosgr.backproject itself is the module; its function of the
+    # same name is nlosgr.backproject.backproject)
+    if name in _BP_NAMES:
+        from . import backproject
+        return getattr(backproject, name)
     raise AttributeError(f"module 'nlosgr' has no attribute {name!r}")

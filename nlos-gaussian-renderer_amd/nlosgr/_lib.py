@@ -66,11 +66,16 @@ class Irf(ctypes.Structure):
     _fields_ = [("ntaps", ctypes.c_int32), ("center", ctypes.c_int32), ("taps", _P), ("background", ctypes.c_float)]
 
 
+class BackprojectOpts(ctypes.Structure):
+    _fields_ = [("r0", ctypes.c_float), ("inv_dr", ctypes.c_float), ("power", ctypes.c_int32),
+                ("accumulate", ctypes.c_int32)]
+
+
 ADAM_MAX_GROUPS = 8  # NLOSGR_ADAM_MAX_GROUPS
 MAX_PER_RAY = 256   # NLOSGR_MAX_PER_RAY
 IRF_MAX_TAPS = 512  # NLOSGR_IRF_MAX_TAPS
 IRF_MAX_NR = 8192   # NLOSGR_IRF_MAX_NR
-ABI_VERSION = 12    # NLOSGR_ABI_VERSION
+ABI_VERSION = 13    # NLOSGR_ABI_VERSION
 
 # nlosgr_options.flags variant selection (NLOSGR_FLAG_*; A/B timing and parity cross-checks, 0 in production)
 FLAG_FLOAT_DRAIN = 0x100   # forward: fp32 claim drain instead of the fixed-point drain
@@ -90,7 +95,7 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_rays_bwd", "nlosgr_rays_analytic", "nlosgr_mse_workspace_bytes", "nlosgr_mse", "nlosgr_adam",
            "nlosgr_irf_apply", "nlosgr_mse_irf_workspace_bytes", "nlosgr_mse_irf",
            "nlosgr_carve_votes", "nlosgr_voxel_workspace_bytes", "nlosgr_voxelize", "nlosgr_volume_project",
-           "nlosgr_mesh_workspace_bytes", "nlosgr_mesh_count", "nlosgr_mesh_emit",
+           "nlosgr_mesh_workspace_bytes", "nlosgr_mesh_count", "nlosgr_mesh_emit", "nlosgr_backproject",
            "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
@@ -160,6 +165,9 @@ def load():
     lib.nlosgr_mesh_emit.argtypes = [_P, _P, PVG, ctypes.c_float, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P,
                                      _P, _P, _P]
     lib.nlosgr_mesh_emit.restype = ctypes.c_int
+    lib.nlosgr_backproject.argtypes = [_P, _P, ctypes.c_int32, ctypes.c_int32, PVG, ctypes.POINTER(BackprojectOpts),
+                                       _P, _P]
+    lib.nlosgr_backproject.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

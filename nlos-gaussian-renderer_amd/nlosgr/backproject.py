@@ -1,0 +1,169 @@
+"""Back-projection of a confocal capture onto a voxel grid: the capture itself in the hidden volume.
+
+Every NLOS reconstruction is compared with it, it is the standard sanity check of a capture file (geometry,
+deltaT, the wall order after data_shuffle), and it is a robust initial density (nlosgr.init.
+sample_from_backprojection).  For voxel centre x and wall point i with histogram h_i (include/nlosgr.h, ABI 13):
+
+    d = |x - wall_i|,  u = (d - r0) / dr,  k = floor(u),  f = u - k
+    out(x) = sum_i d^power ((1-f) h_i[k] + f h_i[k+1])          h_i[j] = 0 outside [0, nr)
+
+r0 is the radius of bin 0 of the rows and dr = c deltaT the bin width, in the units of the renderer's radial
+grid.  One HIP pass (nlosgr_backproject: 8^3 bricks, wall points streamed through LDS, fixed summation order, no
+atomics): bitwise repeatable, and a sub-grid (VoxelGrid.slice) gives exactly the numbers of the full grid.  The
+volume feeds the parts that take any [nx, ny, nz] tensor: voxelize.project / front_view, mesh.isosurface /
+write_ply.  Filtered back-projection filters the rows along time first, through the IRF path:
+
+    backproject(irf_apply(rows, time_filter("log", sigma_bins=2.0)), walls, grid, r0, dr)
+
+No CPU fallback, no backward.
+
+    python -m nlosgr.backproject CAPTURE.mat --resolution 128 --start S --end E [--power P]
+        [--filter none|laplacian|log] [--sigma-bins B] --out bp.npz [--mesh bp.ply --level-frac F]
+"""
+import argparse
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .irf import IRF, irf_apply
+from .voxelize import VoxelGrid, front_view
+
+FILTERS = ("none", "laplacian", "log")
+
+
+def _gpu_f32(t, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise RuntimeError(f"nlosgr: {what} needs float32 GPU tensors (no CPU fallback)")
+    return t.detach().contiguous()
+
+
+def fp32_window(r0, dr):
+    """(r0, inv_dr) as the fp32 values nlosgr_backproject computes with: r0 rounded to fp32 and the fp32
+    quotient 1 / dr (a float64 check of a result has to start from these two)."""
+    return float(np.float32(r0)), float(np.float32(1.0) / np.float32(dr))
+
+
+@torch.no_grad()
+def backproject(rows, walls, grid, r0, dr, power=0, out=None, accumulate=False):
+    """[nx, ny, nz] fp32: the back-projection of rows [nwall, nr] (the layout data.volume_target returns)
+    measured at walls [nwall, 3] onto `grid` (voxelize.VoxelGrid).  r0: radius of bin 0; dr: bin width;
+    power 0..4: weight d^power (falloff compensation).  out: an [nx, ny, nz] tensor to write (accumulate=False)
+    or to add this call's sum to (accumulate=True: a wall back-projected in batches or per rank; one more
+    rounding per call, so close to, not bitwise equal to, one call)."""
+    lib = _lib.load()
+    rows, walls = _gpu_f32(rows, "backproject"), _gpu_f32(walls, "backproject")
+    if rows.dim() != 2 or walls.dim() != 2 or walls.shape[1] != 3 or walls.shape[0] != rows.shape[0]:
+        raise ValueError("nlosgr: backproject takes rows [nwall, nr] and walls [nwall, 3]")
+    if not isinstance(grid, VoxelGrid):
+        raise TypeError("nlosgr: grid must be a voxelize.VoxelGrid")
+    dev = rows.device
+    shape = grid.shape
+    if out is None:
+        if accumulate:
+            raise ValueError("nlosgr: accumulate=True needs the volume to add to (out=)")
+        out = torch.empty(shape, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+            raise RuntimeError("nlosgr: backproject needs float32 GPU tensors (no CPU fallback)")
+        if tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"nlosgr: out must be a contiguous {shape} tensor on {dev}")
+    if not float(dr) > 0:
+        raise ValueError("nlosgr: dr must be > 0")
+    xs, ys, zs = grid.on(dev)
+    vg = _lib.VoxelGrid(shape[0], shape[1], shape[2], _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(zs))
+    opt = _lib.BackprojectOpts(*fp32_window(r0, dr), int(power), int(bool(accumulate)))
+    _lib.check(lib.nlosgr_backproject(_lib.ptr(rows), _lib.ptr(walls), rows.shape[0], rows.shape[1], ctypes.byref(vg),
+                                      ctypes.byref(opt), _lib.ptr(out), _lib.stream_handle(dev)))
+    return out
+
+
+def time_filter(kind, sigma_bins=2.0):
+    """The time-axis filter of filtered back-projection as an nlosgr.irf.IRF (apply it with irf_apply):
+    "laplacian": minus the second difference, taps [-1, 2, -1], centre 1;
+    "log": the same applied to a normalised Gaussian of sigma_bins, truncated at 4 sigma (Laplacian of
+    Gaussian: the band-pass that keeps a surface's onset and drops the slowly varying background)."""
+    lap = np.array([-1.0, 2.0, -1.0])
+    if kind == "laplacian":
+        return IRF(lap, 1, 0.0)
+    if kind == "log":
+        if not sigma_bins > 0:
+            raise ValueError("nlosgr: sigma_bins must be > 0")
+        n = max(1, int(math.ceil(4.0 * float(sigma_bins))))
+        k = np.arange(-n, n + 1, dtype=np.float64)
+        g = np.exp(-0.5 * (k / float(sigma_bins)) ** 2)
+        return IRF(np.convolve(g / g.sum(), lap), n + 1, 0.0)
+    raise ValueError(f"nlosgr: unknown time filter {kind!r} (laplacian, log)")
+
+
+@torch.no_grad()
+def backproject_capture(data_kwargs, resolution, start, end, power=0, filter="log", sigma_bins=2.0, positive=True):
+    """Back-projection of the capture in data_kwargs (data.make_data_kwargs: the shuffled wall order is the
+    order of both the rows and the wall points) over bins [floor(start), floor(start) + end - start) onto
+    VoxelGrid(volume_position, volume_size, resolution).  filter: "none", "laplacian" or "log" (time_filter);
+    positive: clamp at zero.  Returns {"volume" [nx,ny,nz], "front", "depth" (voxelize.front_view), "grid"}."""
+    from .data import volume_target
+    if filter not in FILTERS:
+        raise ValueError(f"nlosgr: filter must be one of {FILTERS}")
+    I1 = int(np.floor(start))
+    rows = volume_target(data_kwargs, start, int(end - start))
+    walls = data_kwargs["camera_grid_positions"].t().contiguous().float()
+    if filter != "none":
+        rows = irf_apply(_gpu_f32(rows, "backproject_capture"), time_filter(filter, sigma_bins))
+    vp = data_kwargs["volume_position"]
+    grid = VoxelGrid([float(v) for v in vp], float(data_kwargs["volume_size"]), resolution)
+    cdt = float(data_kwargs["c"]) * float(data_kwargs["deltaT"])
+    vol = backproject(rows, walls, grid, I1 * cdt, cdt, power=power)
+    if positive:
+        vol.clamp_(min=0.0)
+    front, depth = front_view(vol, grid)
+    return {"volume": vol, "front": front, "depth": depth, "grid": grid}
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m nlosgr.backproject",
+                                 description="Back-project a confocal capture onto a voxel grid (volume, front view, depth).")
+    ap.add_argument("capture", help="Zaragoza-format .mat file")
+    ap.add_argument("--resolution", type=int, default=128)
+    ap.add_argument("--start", type=int, required=True, help="first time bin")
+    ap.add_argument("--end", type=int, required=True, help="one past the last time bin")
+    ap.add_argument("--power", type=int, default=0, choices=range(5), help="weight d^power")
+    ap.add_argument("--filter", choices=FILTERS, default="log")
+    ap.add_argument("--sigma-bins", type=float, default=2.0)
+    ap.add_argument("--out", default="bp.npz")
+    ap.add_argument("--mesh", default=None, help="also write the isosurface as a PLY file")
+    ap.add_argument("--level-frac", type=float, default=0.5, help="isosurface level as a fraction of the maximum")
+    a = ap.parse_args(argv)
+    if a.end <= a.start:
+        ap.error("--end must be greater than --start")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from .data import make_data_kwargs
+    if not torch.cuda.is_available():
+        raise RuntimeError("nlosgr: backproject needs a GPU (no CPU fallback)")
+    dev = torch.device("cuda:0")
+    dk, *_ = make_data_kwargs(a.capture, dev, shuffle=False)
+    out = backproject_capture(dk, a.resolution, a.start, a.end, power=a.power, filter=a.filter, sigma_bins=a.sigma_bins)
+    grid, vol = out["grid"], out["volume"]
+    vp = dk["volume_position"].cpu().numpy().astype(np.float32)
+    # the key names of python -m nlosgr.voxelize (density / albedo both hold the volume; cam as its default)
+    np.savez_compressed(a.out, density=vol.cpu().numpy(), albedo=vol.cpu().numpy(), front=out["front"].cpu().numpy(),
+                        depth=out["depth"].cpu().numpy(), xs=grid.xs.numpy(), ys=grid.ys.numpy(), zs=grid.zs.numpy(),
+                        cam=np.array([vp[0], 0.0, vp[2]], dtype=np.float32))
+    print(f"wrote {a.out}: {grid.shape} voxels, {dk['camera_grid_positions'].shape[1]} wall points, bins "
+          f"[{a.start}, {a.end}), filter {a.filter}, power {a.power}")
+    if a.mesh:
+        from .mesh import isosurface, write_ply
+        level = a.level_frac * float(vol.max())
+        mesh = isosurface(vol, grid, level)
+        write_ply(a.mesh, mesh)
+        print(f"wrote {a.mesh}: level {level:.6g}, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles")
+
+
+if __name__ == "__main__":
+    main()

@@ -7,6 +7,10 @@ lane = voxel, wall points streamed through LDS), and the first-bounce detection
 (`detect_first_bounces`, :38-49, a double Python loop over the wall) is one vectorised torch pass.
 Meshing (`exact_mesh_samping=True`) needs open3d/trimesh, which the reference imports and this
 image lacks: it raises.
+
+`sample_from_backprojection` is an addition without a counterpart in the reference: it draws the initial
+points from the capture's back-projection (nlosgr.backproject) instead of a carved set, so it does not depend
+on a first-bounce threshold and works on captures with a dark-count floor and shot noise.
 """
 import numpy as np
 import torch
@@ -95,4 +99,45 @@ def sample_from_feasible_space_jittering(args, data_kwargs, margin=0.1, rho_scal
     half = spacing / 2.0
     idx = torch.randint(0, coords2.shape[0], (n,), device=coords2.device)
     base = coords2[idx]
+    return base + (torch.rand_like(base) - 0.5) * 2 * half[None], rho
+
+
+@torch.no_grad()
+def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, device="cuda", start=None, end=None,
+                               power=0, filter="log", gamma=1.0):
+    """Data-driven initialisation that does not rest on a first-bounce threshold: init_gaussian_num voxels of
+    the capture's back-projection (nlosgr.backproject.backproject_capture on a carving_volume_size^3 grid,
+    clamped at 0) drawn with torch.multinomial in proportion to volume**gamma, with replacement, and jittered
+    by up to half a grid spacing as the carving sampler does; rho ~ U(0, rho_scale) (numpy), as the other
+    two.  Voxels outside the volume box shrunk by `margin` (the rule of init_rand_points) are not drawn.
+    start / end default to args.start / args.end, or the whole capture.  Returns (points [n,3], rho [n,1])."""
+    from .backproject import backproject_capture
+    n = args.init_gaussian_num
+    rho = np.random.rand(n, 1) * rho_scale
+    if start is None:
+        start = getattr(args, "start", 0)
+    if end is None:
+        end = getattr(args, "end", None)
+        if end is None:
+            end = data_kwargs["nlos_data"].shape[0]
+    res = args.carving_volume_size
+    out = backproject_capture(data_kwargs, res, start, end, power=power, filter=filter, positive=True)
+    vol, grid = out["volume"], out["grid"]
+    dev = vol.device
+    pmin, pmax = data_kwargs["pmin"][:3].to(dev), data_kwargs["pmax"][:3].to(dev)
+    lo = pmin + (pmin * margin).abs()
+    hi = pmax - (pmax * margin).abs()
+    xs, ys, zs = grid.on(dev)
+    inside = (((xs >= lo[0]) & (xs <= hi[0]))[:, None, None] & ((ys >= lo[1]) & (ys <= hi[1]))[None, :, None]
+              & ((zs >= lo[2]) & (zs <= hi[2]))[None, None, :])
+    w = torch.where(inside, vol, torch.zeros_like(vol)).reshape(-1).double()
+    if gamma != 1.0:
+        w = w ** gamma
+    if not bool(torch.isfinite(w).all()) or not float(w.sum()) > 0:
+        raise RuntimeError("nlosgr: the back-projection is zero (or not finite) inside the margin box: nothing to "
+                           "sample from (check start / end, the filter and the capture's geometry)")
+    idx = torch.multinomial(w / w.sum(), n, replacement=True)
+    ny, nz = vol.shape[1], vol.shape[2]
+    base = torch.stack((xs[idx // (ny * nz)], ys[(idx // nz) % ny], zs[idx % nz]), dim=1)
+    half = ((pmax - pmin) / (res - 1)) / 2.0
     return base + (torch.rand_like(base) - 0.5) * 2 * half[None], rho
