@@ -79,7 +79,7 @@ inline BatchBudgets& batch_budgets() {
 // ------------------------------------------------------------------------------------------
 // preprocess: raw params -> A = diag(1/s~) R', sigma, s_max, N = A^T A
 // ------------------------------------------------------------------------------------------
-// fxb / fxinfo (the forward's fixed-point drain, nlosgr_volume.hip kFxBits): a Gaussian whose amplitude bound
+// fxb / fxinfo (the forward's fixed-point drain, nlosgr_volume_fwd.hip kFxBits): a Gaussian whose amplitude bound
 // reaches 2^24 units (fxb[i] x 2^E x 1.002 >= 2^24, E = fxinfo[0]) is stored with a negative sigma, so the
 // main fixed-point launch skips it (w = sigma rho <= 0) and the bright launch takes |sigma|
 template <int PRESET>

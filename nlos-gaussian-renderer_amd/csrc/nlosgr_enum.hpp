@@ -1,4 +1,4 @@
-// Trip plan of the forward's run-following enumeration (nlosgr_volume.hip, enumerate_runs).
+// Trip plan of the forward's run-following enumeration (nlosgr_volume_fwd.hip, enumerate_runs).
 //
 // A trip tests up to kTripCells consecutive cells of ONE row of a pair's candidate box.  Its passing cells
 // are appended to the ray queue as groups of up to K adjacent cells; one group is one queue entry and is

@@ -1,6 +1,6 @@
 // Ray-tile engine (gfx950): per-ray compositing over the batched spherical geometry.
 //
-// It serves the two path C semantics the pair-major kernels of nlosgr_volume.hip cannot express,
+// It serves the two path C semantics the pair-major kernels of nlosgr_volume_fwd.hip / _bwd.hip cannot express,
 // because both make a sample's value depend on the other Gaussians of the same ray:
 //   * NLOSGR_MODE_OCCL — shared transmittance (volume_renderer.cu:80-137): per ray,
 //       D_k = sum_g sigma_g pdf_g(x_k),  W_k = sum_g rho_g (1 - exp(-sigma_g pdf_g(x_k) c dT)),

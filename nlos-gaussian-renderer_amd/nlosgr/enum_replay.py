@@ -1,4 +1,4 @@
-"""Float64 replay, on the CPU, of the forward's candidate enumeration (csrc/nlosgr_volume.hip): the bounding-sphere
+"""Float64 replay, on the CPU, of the forward's candidate enumeration (csrc/nlosgr_volume.hpp, csrc/nlosgr_volume_fwd.hip): the bounding-sphere
 (theta, phi) box of pair_setup, the support of ray_setup (quadric test, [kl, kh]) and the way passing cells are
 grouped into ray queue entries: today's parent scheme ("trip": row-major trips of 3 cells that wrap across rows,
 two adjacent passing cells of a trip pair up) and the run-following scheme of enumerate_runs ("run": trips of 4

@@ -1,14 +1,14 @@
 """Accuracy of the C3 forward at full Ng (diagnostic): the whole-volume forward with the float claim drain
-(NLOSGR_FFX=0) and with the fixed-point drain (default), in the given and in TrainStep's slab order,
+(_lib.FLAG_FLOAT_DRAIN) and with the fixed-point drain (default), in the given and in TrainStep's slab order,
 against the float64 sum of HIP sub-histograms of 250-Gaussian chunks at a few wall points.
 
     python scripts/fx_accuracy.py [--walls 4] [--chunk 250]
 Prints one JSON line."""
-import argparse, json, os, sys
+import argparse, dataclasses, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'nlos-gaussian-renderer_amd')); sys.path.insert(0, ROOT)
 import torch
-from nlosgr import GaussianParams, features_flat
+from nlosgr import GaussianParams, _lib, features_flat
 from nlosgr.render import render_forward
 from nlosgr.train import slab_order
 from nlosgr.volume import Scene, make_config
@@ -29,16 +29,9 @@ idx = torch.linspace(0, H * H - 1, a.walls + 2, device=dev).long()[1:-1]
 gsel = scene.geometry(dev, 'cuda', 'noocl', walls=geo.wall[idx].contiguous())
 
 
-def fwd(params, g, env):
-    old = os.environ.get('NLOSGR_FFX')
-    os.environ['NLOSGR_FFX'] = env
-    try:
-        return render_forward(*params, g, cfg)[0]
-    finally:
-        if old is None:
-            os.environ.pop('NLOSGR_FFX')
-        else:
-            os.environ['NLOSGR_FFX'] = old
+def fwd(params, g, fx):
+    c = cfg if fx == '1' else dataclasses.replace(cfg, flags=_lib.FLAG_FLOAT_DRAIN)
+    return render_forward(*params, g, c)[0]
 
 
 ref = torch.zeros(len(idx), T, dtype=torch.float64, device=dev)

@@ -3,11 +3,11 @@ dense fp32 evaluation against float64 sums of 250-Gaussian HIP sub-histograms (d
 
     python scripts/fx_accuracy_c2.py [--config C2]
 Prints one JSON line."""
-import argparse, json, os, sys
+import argparse, dataclasses, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'nlos-gaussian-renderer_amd')); sys.path.insert(0, ROOT)
 import torch
-from nlosgr import GaussianParams, features_flat
+from nlosgr import GaussianParams, _lib, features_flat
 from nlosgr.render import render_forward
 from nlosgr.volume import Scene, make_config
 
@@ -27,11 +27,8 @@ den = make_config(m, scene, 'cuda', 'noocl', cutoff=0.0)
 
 
 def fwd(params, cfg, ffx='1'):
-    os.environ['NLOSGR_FFX'] = ffx
-    try:
-        return render_forward(*params, geo, cfg)[0].double()
-    finally:
-        os.environ.pop('NLOSGR_FFX')
+    c = cfg if ffx == '1' else dataclasses.replace(cfg, flags=_lib.FLAG_FLOAT_DRAIN)
+    return render_forward(*params, geo, c)[0].double()
 
 
 refs = {}

@@ -1,7 +1,7 @@
 """VGPR count and scratch bytes per kernel of a -save-temps device assembly (build.py --save-temps leaves
-nlosgr_<file>-hip-amdgcn-amd-amdhsa-gfx950.s in csrc/).
+nlosgr_<file>-hip-amdgcn-amd-amdhsa-gfx950.s in csrc/), e.g. of nlosgr_volume_fwd or nlosgr_volume_bwd.
 
-    python scripts/kernel_regs.py nlos-gaussian-renderer_amd/csrc/nlosgr_volume-hip-amdgcn-amd-amdhsa-gfx950.s [filter]"""
+    python scripts/kernel_regs.py nlos-gaussian-renderer_amd/csrc/nlosgr_volume_bwd-hip-amdgcn-amd-amdhsa-gfx950.s [filter]"""
 import re, sys
 
 s = open(sys.argv[1]).read()

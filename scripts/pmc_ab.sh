@@ -1,5 +1,5 @@
 # SQ counter passes over one C3 forward per variant (scripts/ab_env.py --reps 0), e.g.
-#   bash scripts/pmc_ab.sh "--cutoff 5.7" NLOSGR_FREG=0 NLOSGR_FREG=1
+#   bash scripts/pmc_ab.sh "--cutoff 5.7 --flags 0x100" -
 set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/pmc_ab; mkdir -p $O

@@ -1,5 +1,5 @@
 """CPU replay of the forward's enumeration and segment geometry: what grouping adjacent rays into one lane
-(csrc/nlosgr_volume.hip, enumerate_runs and fx_twin_setup) saves at a benchmark configuration.
+(csrc/nlosgr_volume_fwd.hip, enumerate_runs and fx_twin_setup) saves at a benchmark configuration.
 
 For a sample of (wall point, Gaussian) pairs of the seeded C3 scene it evaluates, in float64, the kernel's own
 bounding-sphere box (pair_setup) and support formulas (ray_setup: closest approach, m2min, [kl, kh]) through

@@ -127,6 +127,90 @@ def test_occl_row_cache_size_matches_library(nwall, nt, np_, nr):
     assert sizes[1] - sizes[0] == (want + 255) // 256 * 256
 
 
+# (ng, nwall, nt, np, nr, mode, preset, ray_cache, nsplit, flags, drho_mb, bytes): nlosgr_workspace_bytes of the
+# pair-major path as the library gave it before its workspace arithmetic moved into one layout struct
+# (cutoff 5.7, c_deltaT 1e-3, k_feat 16, degree 3; SH / PW = NLOSGR_FLAG_BWD_SHARED / _PERWAVE)
+_SH, _PW = 0x1000, 0x2000
+_VOLUME_WS_BYTES = [
+    (0, 1024, 32, 32, 1024, 0, 1, 0, 0, 0, None, 8390912),
+    (0, 1024, 32, 32, 1024, 1, 0, 1, 0, 0, None, 8390912),
+    (1, 1024, 32, 32, 1024, 0, 1, 0, 0, 0, None, 8527360),
+    (1, 1024, 32, 32, 1024, 1, 0, 1, 0, 0, None, 8551936),
+    (255, 1024, 32, 32, 1024, 0, 1, 0, 0, 0, None, 42995712),
+    (255, 1024, 32, 32, 1024, 1, 0, 1, 0, 0, None, 49262592),
+    (256, 1024, 32, 32, 1024, 0, 1, 0, 0, 0, None, 43131136),
+    (256, 1024, 32, 32, 1024, 1, 0, 1, 0, 0, None, 49422592),
+    (257, 1024, 32, 32, 1024, 0, 1, 0, 0, 0, None, 43267584),
+    (257, 1024, 32, 32, 1024, 1, 0, 1, 0, 0, None, 49583616),
+    (1000, 1024, 32, 32, 1024, 0, 1, 0, 0, 0, None, 152483840),
+    (1000, 1024, 32, 32, 1024, 1, 0, 1, 0, 0, None, 177059840),
+    (100000, 1024, 32, 32, 1024, 0, 1, 0, 0, 0, None, 2109556992),
+    (100000, 1024, 32, 32, 1024, 1, 0, 1, 0, 0, None, 4567156992),
+    (1000, 0, 32, 32, 1024, 0, 1, 0, 0, 0, None, 334848),
+    (1000, 0, 32, 32, 1024, 0, 1, 1, 7, 0, None, 334848),
+    (100000, 0, 32, 32, 1024, 1, 1, 0, 0, 0, None, 33202688),
+    (1000, 1, 32, 32, 1024, 0, 1, 0, 0, 0, None, 351232),
+    (1000, 1, 32, 32, 1024, 0, 1, 1, 7, 0, None, 375296),
+    (100000, 1, 32, 32, 1024, 1, 1, 0, 0, 0, None, 33235456),
+    (1000, 3, 32, 32, 1024, 0, 1, 0, 0, 0, None, 647936),
+    (1000, 3, 32, 32, 1024, 0, 1, 1, 7, 0, None, 720128),
+    (100000, 3, 32, 32, 1024, 1, 1, 0, 0, 0, None, 59700992),
+    (1000, 1024, 32, 32, 1024, 0, 1, 1, 7, 0, None, 46883840),
+    (100000, 1024, 32, 32, 1024, 1, 1, 0, 0, 0, None, 2109556992),
+    (1000, 65536, 32, 32, 1024, 0, 1, 0, 0, 0, None, 2379137536),
+    (1000, 65536, 32, 32, 1024, 0, 1, 1, 7, 0, None, 2380033536),
+    (100000, 65536, 32, 32, 1024, 1, 1, 0, 0, 0, None, 3344073472),
+    (1000, 1024, 32, 32, 1, 0, 1, 0, 0, 0, None, 135723008),
+    (1000, 1024, 7, 5, 1, 0, 1, 1, 0, 0, None, 160299008),
+    (257, 1024, 7, 5, 1, 2, 0, 0, 0, 0, None, 34887168),
+    (1000, 1024, 32, 32, 40, 0, 1, 0, 0, 0, None, 136361984),
+    (1000, 1024, 7, 5, 40, 0, 1, 1, 0, 0, None, 160937984),
+    (257, 1024, 7, 5, 40, 2, 0, 0, 0, 0, None, 35206656),
+    (1000, 1024, 7, 5, 1024, 0, 1, 1, 0, 0, None, 177059840),
+    (257, 1024, 7, 5, 1024, 2, 0, 0, 0, 0, None, 43267584),
+    (1000, 1024, 32, 32, 2048, 0, 1, 0, 0, 0, None, 169261056),
+    (1000, 1024, 7, 5, 2048, 0, 1, 1, 0, 0, None, 193837056),
+    (257, 1024, 7, 5, 2048, 2, 0, 0, 0, 0, None, 51656192),
+    (1000, 1024, 32, 32, 4096, 0, 1, 0, 0, 0, None, 202815488),
+    (1000, 1024, 7, 5, 4096, 0, 1, 1, 0, 0, None, 227391488),
+    (257, 1024, 7, 5, 4096, 2, 0, 0, 0, 0, None, 68433408),
+    (100000, 65536, 32, 32, 1024, 0, 0, 0, 0, 0, None, 3344073472),
+    (100000, 65536, 32, 32, 1024, 0, 1, 0, 0, 0, None, 3344073472),
+    (100000, 65536, 32, 32, 1024, 1, 0, 0, 0, 0, None, 3344073472),
+    (100000, 65536, 32, 32, 1024, 2, 0, 0, 0, 0, None, 3344073472),
+    (100000, 65536, 32, 32, 1024, 2, 1, 0, 0, 0, None, 3344073472),
+    (1000, 1024, 32, 32, 1024, 0, 1, 0, 0, _SH, None, 152483840),
+    (257, 3, 32, 32, 1024, 0, 1, 1, 7, _SH, None, 199936),
+    (1000, 1024, 32, 32, 2048, 0, 1, 0, 0, _SH, None, 169261056),
+    (257, 3, 32, 32, 2048, 0, 1, 1, 7, _SH, None, 224512),
+    (1000, 1024, 32, 32, 1024, 0, 1, 0, 0, _PW, None, 152483840),
+    (257, 3, 32, 32, 1024, 0, 1, 1, 7, _PW, None, 199936),
+    (1000, 1024, 32, 32, 2048, 0, 1, 0, 0, _PW, None, 169261056),
+    (257, 3, 32, 32, 2048, 0, 1, 1, 7, _PW, None, 224512),
+    (100000, 1024, 32, 32, 1024, 0, 1, 0, 0, 0, 1.0, 79956992),
+    (100000, 65536, 32, 32, 1024, 1, 1, 1, 0, 0, 1.0, 157869673472),
+    (1000, 1024, 32, 32, 1024, 0, 1, 0, 0, 0, 1.0, 51564032),
+]
+
+
+def test_volume_workspace_bytes_are_the_recorded_layout():
+    """The pair-major workspace is sized byte for byte as recorded: every Gaussian and wall count around the
+    256-Gaussian blocks, short and long rows, the three modes and both presets, the ray cache, a forced
+    split count, both forced backward layouts and a 1 MiB dL/drho batch budget (host-only call, no GPU)."""
+    import contextlib
+    from nlosgr import _lib
+    lib = _lib.load()
+    fake = ctypes.c_void_p(4096)   # validation only checks that the pointers are set
+    got = []
+    for ng, nwall, nt, np_, nr, mode, preset, cache, nsplit, flags, drho_mb, _ in _VOLUME_WS_BYTES:
+        g = _lib.Gaussians(ng, 16, 3, preset, 1.0, fake, fake, fake, fake, fake)
+        geo = _lib.Geometry(nwall, nt, np_, nr, *([fake] * 9))
+        opt = _lib.Options(mode, 5.7, 0.001, 1.0, nsplit, flags, cache, _lib.SELECT_SUPPORT, 0, 0)
+        with _lib.batch_budgets(drho_mb=drho_mb) if drho_mb else contextlib.nullcontext():
+            got.append(lib.nlosgr_workspace_bytes(g, geo, opt))
+    assert got == [row[-1] for row in _VOLUME_WS_BYTES]
+
+
 def test_batch_budgets_restore_the_values_in_effect():
     """batch_budgets restores the budgets that were in effect (nlosgr_get_batch_budgets),
     not the environment's defaults, so nested contexts and direct nlosgr_set_batch_budgets calls survive."""

@@ -1,4 +1,4 @@
-"""Per-Gaussian float64 parity of the culled volume backward (bwd_kernel in csrc/nlosgr_volume.hip) at its edges.
+"""Per-Gaussian float64 parity of the culled volume backward (bwd_kernel in csrc/nlosgr_volume_bwd.hip) at its edges.
 
 Every case calls render_forward / render_backward directly and compares all six gradient tensors, Gaussian by
 Gaussian, with the float64 reference of tests/volume_oracle.py in its metric

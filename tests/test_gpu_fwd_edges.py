@@ -1,4 +1,4 @@
-"""Per-bin float64 parity of the culled volume forward (fwd_body and its drains in csrc/nlosgr_volume.hip) at the
+"""Per-bin float64 parity of the culled volume forward (fwd_body and its drains in csrc/nlosgr_volume_fwd.hip) at the
 edges of its drains.  A change to a forward drain is judged by this file.
 
 Every case calls render_forward directly and compares every bin of every wall point with the float64 reference of

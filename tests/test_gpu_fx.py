@@ -1,6 +1,6 @@
 """The fixed-point (FX) forward drain over dynamic range.
 
-The FX drain (csrc/nlosgr_volume.hip, kFxBits) sums every term as an integer count of units 2^-E.  Round 5
+The FX drain (csrc/nlosgr_volume_fwd.hip, kFxBits) sums every term as an integer count of units 2^-E.  Round 5
 took E from the LARGEST amplitude bound of the launch, so a few very bright Gaussians coarsened the unit of
 all others and their sub-half-unit tails rounded to zero.  Round 6 takes E from a quantile of the bounds
 (the ceil(ng/256)-th brightest) and sends the segments of anything brighter through exact u64 adds into the

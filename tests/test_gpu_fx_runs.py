@@ -1,4 +1,4 @@
-"""Run-following pairs of the no-occlusion fixed-point (FX) forward (csrc/nlosgr_volume.hip, enumerate_runs;
+"""Run-following pairs of the no-occlusion fixed-point (FX) forward (csrc/nlosgr_volume_fwd.hip, enumerate_runs;
 csrc/nlosgr_enum.hpp, trip_plan).
 
 The enumeration tests 4 cells of one row of a pair's box per trip and pairs passing cells along their run, so a

@@ -1,4 +1,4 @@
-"""The twin drain of the no-occlusion fixed-point (FX) forward (csrc/nlosgr_volume.hip, fx_twin_setup).
+"""The twin drain of the no-occlusion fixed-point (FX) forward (csrc/nlosgr_volume_fwd.hip, fx_twin_setup).
 
 By default a lane of the FX drain takes two adjacent rays (i, j), (i, j + 1) of one (wall point, Gaussian) pair,
 walks the union of their bin ranges and adds the two values of every bin with one LDS atomic;

@@ -301,7 +301,7 @@ def forward_worst(hist, ref):
 # --------------------------------------------------------------------------------------------
 U = 2.0 ** -24          # fp32 unit roundoff
 C_FWD = 32.0            # the forward's position allowance C_FWD m_c |u0| U (derived in test_gpu_bwd_edges.py)
-FX_BITS = 24            # kFxBits of csrc/nlosgr_volume.hip
+FX_BITS = 24            # kFxBits of csrc/nlosgr_volume_fwd.hip
 # Four times the worst per-bin value measured on the MI355X over scenes 1, 4 and 5 of test_gpu_fwd_edges.py (1.6e-5,
 # table in that file) would be 7e-5; the constant stays at 2e-5, the row tolerance it replaces, which leaves a margin
 # of 1.25 instead of 4.  The excess is traced to the drains' exp2 recurrence (that file's docstring), not fixed here.
