@@ -20,6 +20,8 @@
  *                          main.py:203-213 (torch.optim.Adam groups, gaussian_model.py:223-242)
  *   nlosgr_irf_apply / nlosgr_mse_irf: no counterpart (the reference trains on synthetic transients only);
  *                          the detector's temporal response between the render and a measured capture
+ *   nlosgr_loss_irf     no counterpart: the same fused loss with a kind, the MSE or the Poisson deviance of
+ *                          photon counts
  *   nlosgr_bboxes       <- compute_gaussian_bboxes_kernel include/bbox_compute.cuh:76-120,
  *                          GaussianModel.get_bboxes gaussian_model/gaussian_model.py:140-178
  *   nlosgr_carve_votes  <- the voting loop of space_carving gaussian_model/gaussian_utils.py:88-99
@@ -334,6 +336,50 @@ NLOSGR_API size_t nlosgr_mse_irf_workspace_bytes(long long rows);
 NLOSGR_API int nlosgr_mse_irf(const float* hist, const float* target, float gt_times, long long rows, int32_t nr,
                    const nlosgr_irf* irf, float grad_scale, float* grad_out, void* workspace, float* loss_out,
                    void* hip_stream);
+
+/* Photon-count likelihood (an addition to ABI 13: two new symbols and one new struct; nothing existing changes
+ * its signature or layout, so the ABI number stays).  A measured transient is a histogram of photon counts: its
+ * noise is Poisson, the variance of a bin is its rate, and the MSE (the likelihood of constant-variance Gaussian
+ * noise) puts nearly all its weight on the bright first-return peak.  The fused loss takes a kind:
+ *   NLOSGR_LOSS_MSE      nlosgr_mse_irf bit for bit (the same kernel instantiation; rate_floor is ignored)
+ *   NLOSGR_LOSS_POISSON  per element, with lambda = apply(hist) (background included), t the target and
+ *                        eps = rate_floor > 0:
+ *       y'  = max(gt_times t, 0) + eps           measured counts plus the floor
+ *       rho = max(lambda, 0) + eps               model rate plus the same floor
+ *       dev = 2 [y' log(y'/rho) - (y' - rho)]    the Poisson deviance: >= 0, and 0 exactly when rho = y'
+ *       dL/dlambda = (2 / n) (rho - y') / rho  where lambda >= 0, else 0
+ *     No special case for empty bins (y' >= eps > 0).  With non-negative taps, render and background the clamp
+ *     on lambda never acts; it keeps filters with negative taps from producing NaN.
+ *     loss_out[4] = {sum dev / n, sum dev / sum max(gt t, 0) (deviance per measured count; 0 without counts),
+ *     sum dev, sum max(gt t, 0)}: the {a/n, a/b, a, b} of the MSE's four floats, so the ranks of a sharded volume
+ *     and the batches of a wall combine [2] and [3] the same way.
+ *     grad_out (may be NULL) = adjoint(grad_scale dL/dlambda) = dL/dhist, which nlosgr_render_bwd takes unchanged.
+ *     Element sequence, one fp32 operation each and no contraction, so that the error can be bounded:
+ *       y = gt t;  y' = max(y, 0) + eps;  rho = max(lambda, 0) + eps;  r = rho - y';
+ *       z = lambda >= 0 ? gscale (r / rho) : 0          (gscale = grad_scale 2 / n, formed in double)
+ *       e = r / y';  dev = 2 y' (e - log1pf(e))
+ *     (rho - y') / rho and not 1 - y'/rho: the subtraction is exact where the fit is good.  e is held at the
+ *     float above -1: where rho < 2^-25 y' the fp32 r is -y', the reported deviance is then about 31 y' and no
+ *     longer grows with log(y'/rho); the gradient is unaffected.
+ * rate_floor: the capture's dark-count level is the natural value, with gt_times the knob that brings the capture
+ * to counts; one pseudo-count keeps the gradient of a bin the render does not reach yet at about -y, not -y / eps.
+ * One pass, no atomics, no LDS beyond nlosgr_mse_irf's; the two per-row partials go through the same tree and are
+ * added in double in row order: bitwise repeatable, and independent of how rows are split over calls.
+ * Errors: a null loss, an unknown kind, or (POISSON) a rate_floor that is not finite or not > 0: NLOSGR_E_INVALID;
+ * the rest as nlosgr_mse_irf (nr > NLOSGR_IRF_MAX_NR: NLOSGR_E_UNSUPPORTED).  rows == 0 is valid and gives zeros.
+ * workspace: nlosgr_loss_irf_workspace_bytes(rows) bytes, the size nlosgr_mse_irf_workspace_bytes gives. */
+#define NLOSGR_LOSS_MSE 0
+#define NLOSGR_LOSS_POISSON 1
+
+typedef struct nlosgr_loss {
+    int32_t kind;             /* NLOSGR_LOSS_* */
+    float rate_floor;         /* POISSON: eps, finite and > 0 */
+} nlosgr_loss;                /* 8 bytes */
+
+NLOSGR_API size_t nlosgr_loss_irf_workspace_bytes(long long rows);
+NLOSGR_API int nlosgr_loss_irf(const float* hist, const float* target, float gt_times, long long rows, int32_t nr,
+                    const nlosgr_irf* irf, const nlosgr_loss* loss, float grad_scale, float* grad_out,
+                    void* workspace, float* loss_out, void* hip_stream);
 
 /* One torch.optim.Adam step (no weight decay, no amsgrad) over 1..NLOSGR_ADAM_MAX_GROUPS parameter
  * groups; `step` >= 1 is the step count including this update (bias correction).  The scalars are

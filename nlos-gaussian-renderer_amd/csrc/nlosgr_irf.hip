@@ -1,5 +1,6 @@
 // Temporal instrument response (gfx950): the convolution in time between a rendered transient and a
-// measured one, its adjoint, and the volume MSE fused with both (include/nlosgr.h, ABI 12).
+// measured one, its adjoint, and the volume loss fused with both: the MSE (include/nlosgr.h, ABI 12) or the
+// Poisson deviance of photon counts (nlosgr_loss_irf).
 //
 //   apply:    y[p,t] = b + sum_j w[j] h[p, t + c - j]        adjoint:  g[p,s] = sum_j w[j] z[p, s - c + j]
 //
@@ -17,6 +18,8 @@
 //   * fused loss: y goes back to the LDS image, a coalesced pass reads the target, forms d, the loss
 //     partials and z = gscale d in place, then the adjoint runs from the same image and the result
 //     leaves through a coalesced pass.  hist and target are read once, grad_out is written once.
+//     The Poisson kind differs in that pass alone (the deviance and z = gscale (rho - y') / rho per element):
+//     same LDS, same two partials per row, same tree.
 //   * the loss sums are per-row partials (block tree as mse_kernel) in the workspace; the finish kernel
 //     adds them in double, 256 consecutive row blocks each in row order, then the blocks in order.
 // No atomics: every output depends on its own row only, whatever the schedule.
@@ -39,6 +42,7 @@ struct IrfArgs {
     long long rows;
     int nr, L, c, adjoint;
     float b, gt, gscale;
+    float eps;              // NLOSGR_LOSS_POISSON: rate_floor
 };
 
 __host__ __device__ constexpr int irf_log(int R) { return R == 8 ? 3 : 2; }
@@ -108,7 +112,8 @@ __device__ __forceinline__ void irf_conv(float* buf, const float* tl, int W, int
     __syncthreads();
 }
 
-template <int R, int NC, bool FUSED>
+// LOSS (NLOSGR_LOSS_*) is read in the FUSED branch only
+template <int R, int NC, bool FUSED, int LOSS>
 __global__ __launch_bounds__(kBlock) void irf_kernel(IrfArgs a) {
     extern __shared__ float lds[];
     const int tid = threadIdx.x;
@@ -139,13 +144,33 @@ __global__ __launch_bounds__(kBlock) void irf_kernel(IrfArgs a) {
             irf_conv<R, NC>(buf, tlf, W, Lpad, a.c, a.nr, a.b);
             const float* target = a.target + row * a.nr;
             float se = 0.f, st = 0.f;
-            for (int i = tid; i < a.nr; i += kBlock) {
-                const int p = irf_phys<R>(Lpad + i, W);
-                const float t = target[i] * a.gt;
-                const float d = buf[p] - t;
-                se = fmaf(d, d, se);
-                st = fmaf(t, t, st);
-                buf[p] = a.gscale * d;
+            if (LOSS == NLOSGR_LOSS_POISSON) {
+                // one fp32 rounding per operation, in the order include/nlosgr.h gives (no contraction):
+                // tests/loss_oracle.py bounds the gradient's error by counting them
+#pragma clang fp contract(off)
+                for (int i = tid; i < a.nr; i += kBlock) {
+                    const int p = irf_phys<R>(Lpad + i, W);
+                    const float lam = buf[p];
+                    const float y = a.gt * target[i];
+                    const float yp = fmaxf(y, 0.f) + a.eps;
+                    const float rho = fmaxf(lam, 0.f) + a.eps;
+                    const float r = rho - yp;
+                    buf[p] = lam >= 0.f ? a.gscale * (r / rho) : 0.f;
+                    // e > -1 in exact arithmetic; r rounds to -y' once rho < 2^-25 y', and log1pf(-1) = -inf
+                    const float e = fmaxf(r / yp, -0x1.fffffep-1f);
+                    const float dev = 2.f * yp * (e - log1pf(e));
+                    se = se + dev;
+                    st = st + fmaxf(y, 0.f);
+                }
+            } else {
+                for (int i = tid; i < a.nr; i += kBlock) {
+                    const int p = irf_phys<R>(Lpad + i, W);
+                    const float t = target[i] * a.gt;
+                    const float d = buf[p] - t;
+                    se = fmaf(d, d, se);
+                    st = fmaf(t, t, st);
+                    buf[p] = a.gscale * d;
+                }
             }
             red[tid] = se;
             red[kBlock + tid] = st;
@@ -198,20 +223,20 @@ __global__ __launch_bounds__(kBlock) void irf_finish_kernel(const float* __restr
     out[3] = (float)st;
 }
 
-template <int R, int NC, bool FUSED>
+template <int R, int NC, bool FUSED, int LOSS>
 void irf_launch_cfg(const IrfArgs& a, hipStream_t s) {
     const int W = irf_width<R>(irf_span<R>(a.nr, a.L));
     const size_t lds = (size_t)(R * W + kFixedLds) * sizeof(float);   // <= 45.3 KB at nr 8192, 512 taps
     const int grid = (int)(a.rows < kMaxGrid ? a.rows : kMaxGrid);
-    hipLaunchKernelGGL((irf_kernel<R, NC, FUSED>), dim3(grid), dim3(kBlock), lds, s, a);
+    hipLaunchKernelGGL((irf_kernel<R, NC, FUSED, LOSS>), dim3(grid), dim3(kBlock), lds, s, a);
 }
 
-template <bool FUSED>
+template <bool FUSED, int LOSS = NLOSGR_LOSS_MSE>
 void irf_launch(const IrfArgs& a, hipStream_t s) {
-    if (a.nr <= 4 * kBlock) irf_launch_cfg<4, 1, FUSED>(a, s);
-    else if (a.nr <= 8 * kBlock) irf_launch_cfg<8, 1, FUSED>(a, s);
-    else if (a.nr <= 16 * kBlock) irf_launch_cfg<8, 2, FUSED>(a, s);
-    else irf_launch_cfg<8, 4, FUSED>(a, s);
+    if (a.nr <= 4 * kBlock) irf_launch_cfg<4, 1, FUSED, LOSS>(a, s);
+    else if (a.nr <= 8 * kBlock) irf_launch_cfg<8, 1, FUSED, LOSS>(a, s);
+    else if (a.nr <= 16 * kBlock) irf_launch_cfg<8, 2, FUSED, LOSS>(a, s);
+    else irf_launch_cfg<8, 4, FUSED, LOSS>(a, s);
 }
 
 int irf_validate(const nlosgr_irf* irf, long long rows, int32_t nr) {
@@ -223,6 +248,15 @@ int irf_validate(const nlosgr_irf* irf, long long rows, int32_t nr) {
     if (rows < 0) return set_err(NLOSGR_E_INVALID, "rows must be >= 0");
     if (nr < 1) return set_err(NLOSGR_E_INVALID, "nr must be >= 1");
     if (nr > NLOSGR_IRF_MAX_NR) return set_err(NLOSGR_E_UNSUPPORTED, "nr > NLOSGR_IRF_MAX_NR");
+    return NLOSGR_OK;
+}
+
+int loss_validate(const nlosgr_loss* loss) {
+    if (!loss) return set_err(NLOSGR_E_INVALID, "null loss");
+    if (loss->kind != NLOSGR_LOSS_MSE && loss->kind != NLOSGR_LOSS_POISSON)
+        return set_err(NLOSGR_E_INVALID, "loss.kind must be NLOSGR_LOSS_MSE or NLOSGR_LOSS_POISSON");
+    if (loss->kind == NLOSGR_LOSS_POISSON && !(isfinite(loss->rate_floor) && loss->rate_floor > 0.f))
+        return set_err(NLOSGR_E_INVALID, "loss.rate_floor must be finite and > 0");
     return NLOSGR_OK;
 }
 
@@ -245,13 +279,14 @@ int nlosgr_irf_apply(const float* x, long long rows, int32_t nr, const nlosgr_ir
     return NLOSGR_OK;
 }
 
-size_t nlosgr_mse_irf_workspace_bytes(long long rows) {
+size_t nlosgr_loss_irf_workspace_bytes(long long rows) {
     return align_up((size_t)2 * sizeof(float) * (size_t)(rows > 0 ? rows : 1));
 }
 
-int nlosgr_mse_irf(const float* hist, const float* target, float gt_times, long long rows, int32_t nr,
-                   const nlosgr_irf* irf, float grad_scale, float* grad_out, void* workspace, float* loss_out,
-                   void* hip_stream) {
+int nlosgr_loss_irf(const float* hist, const float* target, float gt_times, long long rows, int32_t nr,
+                    const nlosgr_irf* irf, const nlosgr_loss* loss, float grad_scale, float* grad_out, void* workspace,
+                    float* loss_out, void* hip_stream) {
+    if (int rc = loss_validate(loss)) return rc;
     if (int rc = irf_validate(irf, rows, nr)) return rc;
     if (!loss_out || !workspace) return set_err(NLOSGR_E_INVALID, "null loss/workspace pointer");
     if (rows > 0 && (!hist || !target)) return set_err(NLOSGR_E_INVALID, "null hist/target pointer");
@@ -263,12 +298,28 @@ int nlosgr_mse_irf(const float* hist, const float* target, float gt_times, long 
         a.in = hist; a.target = target; a.taps = irf->taps; a.out = grad_out; a.partial = (float*)workspace;
         a.rows = rows; a.nr = nr; a.L = irf->ntaps; a.c = irf->center; a.b = irf->background; a.gt = gt_times;
         a.gscale = (float)((double)grad_scale * 2.0 / n);
-        irf_launch<true>(a, s);
+        if (loss->kind == NLOSGR_LOSS_POISSON) {
+            a.eps = loss->rate_floor;
+            irf_launch<true, NLOSGR_LOSS_POISSON>(a, s);
+        } else {
+            irf_launch<true, NLOSGR_LOSS_MSE>(a, s);
+        }
     }
+    // {a / n, a / b, a, b} of the two sums, whatever the kind
     hipLaunchKernelGGL(irf_finish_kernel, dim3(1), dim3(kBlock), 0, s, (const float*)workspace, rows,
                        rows > 0 ? n : 1.0, loss_out);
     HIPCHK(hipGetLastError());
     return NLOSGR_OK;
+}
+
+size_t nlosgr_mse_irf_workspace_bytes(long long rows) { return nlosgr_loss_irf_workspace_bytes(rows); }
+
+int nlosgr_mse_irf(const float* hist, const float* target, float gt_times, long long rows, int32_t nr,
+                   const nlosgr_irf* irf, float grad_scale, float* grad_out, void* workspace, float* loss_out,
+                   void* hip_stream) {
+    const nlosgr_loss mse = {NLOSGR_LOSS_MSE, 0.f};
+    return nlosgr_loss_irf(hist, target, gt_times, rows, nr, irf, &mse, grad_scale, grad_out, workspace, loss_out,
+                           hip_stream);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@ Layers:
     nlosgr.mesh            surface output: isosurface of a voxelized field as a triangle mesh, PLY export
     nlosgr.backproject     the capture on a voxel grid: back-projection, time filters, backproject_capture
     nlosgr.irf             temporal instrument response: IRF, gaussian_irf, convolve_time (render -> capture)
+    nlosgr.loss            photon-count likelihood: fused loss(kind=), PoissonDeviance, simulate_capture
 """
 from . import _lib  # noqa: F401
 from .geometry import Geometry, build_geometry, relay_wall_grid, volume_box_point  # noqa: F401

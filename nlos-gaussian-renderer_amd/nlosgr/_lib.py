@@ -66,6 +66,15 @@ class Irf(ctypes.Structure):
     _fields_ = [("ntaps", ctypes.c_int32), ("center", ctypes.c_int32), ("taps", _P), ("background", ctypes.c_float)]
 
 
+class Loss(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("rate_floor", ctypes.c_float)]
+
+
+LOSS_MSE = 0      # NLOSGR_LOSS_MSE
+LOSS_POISSON = 1  # NLOSGR_LOSS_POISSON
+LOSSES = {"mse": LOSS_MSE, "poisson": LOSS_POISSON}
+
+
 class BackprojectOpts(ctypes.Structure):
     _fields_ = [("r0", ctypes.c_float), ("inv_dr", ctypes.c_float), ("power", ctypes.c_int32),
                 ("accumulate", ctypes.c_int32)]
@@ -94,6 +103,7 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_bboxes", "nlosgr_rays_workspace_bytes", "nlosgr_filter_rays", "nlosgr_rays_fwd",
            "nlosgr_rays_bwd", "nlosgr_rays_analytic", "nlosgr_mse_workspace_bytes", "nlosgr_mse", "nlosgr_adam",
            "nlosgr_irf_apply", "nlosgr_mse_irf_workspace_bytes", "nlosgr_mse_irf",
+           "nlosgr_loss_irf_workspace_bytes", "nlosgr_loss_irf",
            "nlosgr_carve_votes", "nlosgr_voxel_workspace_bytes", "nlosgr_voxelize", "nlosgr_volume_project",
            "nlosgr_mesh_workspace_bytes", "nlosgr_mesh_count", "nlosgr_mesh_emit", "nlosgr_backproject",
            "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
@@ -146,6 +156,11 @@ def load():
     lib.nlosgr_mse_irf.argtypes = [_P, _P, ctypes.c_float, ctypes.c_longlong, ctypes.c_int32, PIRF, ctypes.c_float,
                                    _P, _P, _P, _P]
     lib.nlosgr_mse_irf.restype = ctypes.c_int
+    lib.nlosgr_loss_irf_workspace_bytes.argtypes = [ctypes.c_longlong]
+    lib.nlosgr_loss_irf_workspace_bytes.restype = ctypes.c_size_t
+    lib.nlosgr_loss_irf.argtypes = [_P, _P, ctypes.c_float, ctypes.c_longlong, ctypes.c_int32, PIRF,
+                                    ctypes.POINTER(Loss), ctypes.c_float, _P, _P, _P, _P]
+    lib.nlosgr_loss_irf.restype = ctypes.c_int
     lib.nlosgr_adam.argtypes = [ctypes.POINTER(AdamGroup), ctypes.c_int32, ctypes.c_longlong, ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, _P]
     lib.nlosgr_adam.restype = ctypes.c_int

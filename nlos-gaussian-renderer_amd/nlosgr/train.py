@@ -8,7 +8,8 @@ iteration for a whole volume (or this rank's band of it) with every piece on the
 host synchronisation inside the step:
 
     render_forward (HIP, records the ray cache)  ->  nlosgr_mse (loss, equal_loss, dL/dhist)
-                                                     [nlosgr_mse_irf when the capture has an IRF]
+                                                     [nlosgr_mse_irf when the capture has an IRF;
+                                                      nlosgr_loss_irf for the photon-count likelihood]
     ->  render_backward (HIP, walks the ray cache)  ->  [one packed all-reduce when sharded]
     ->  nlosgr_adam (all six groups in one launch; position lr from get_expon_lr_func)
 
@@ -23,6 +24,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .loss import loss as fused_loss
 from .model import features_flat
 from .render import render_backward, render_forward, tile_rows_bytes, use_ray_cache
 
@@ -252,14 +254,20 @@ class TrainStep:
     irf     : nlosgr.irf.IRF of the capture (None: an ideal detector, nlosgr_mse as before).  Rows are
               wall points, so a band or a batch of them needs nothing special.  With keep_grads,
               self.hist stays the render before the IRF and self.grad_hist is dL/dhist.
+    loss    : "mse" (the reference's loss, as before) or "poisson" (nlosgr.loss: the Poisson deviance of photon
+              counts, for a measured capture; target * gt_times is then in counts and rate_floor is its floor,
+              naturally the dark-count level).  The returned loss2 is (mean deviance, deviance per count).
     nwall_total : wall points of the whole volume (the MSE is normalised over the whole volume and
               the band gradients / losses are summed over ranks).
     """
 
     def __init__(self, model, geo, cfg, target, gt_times=1.0, opt=None, spatial_lr_scale=1.0, nwall_total=None,
                  group=None, sh_schedule=False, events=None, buckets=4, keep_grads=False, bwd_order="slab",
-                 fwd_order="slab", irf=None):
+                 fwd_order="slab", irf=None, loss="mse", rate_floor=1.0):
         self.model, self.geo, self.cfg = model, geo, cfg
+        if loss not in _lib.LOSSES:
+            raise ValueError(f"nlosgr: loss must be one of {tuple(_lib.LOSSES)}, got {loss!r}")
+        self.loss_kind, self.rate_floor = loss, float(rate_floor)
         # the capture's temporal response (nlosgr.irf.IRF): every loss of the step compares the target with
         # the IRF applied to the render; a property of the capture, so checkpoints do not store it
         self.irf = irf.to(model._mu.device) if irf is not None else None
@@ -382,8 +390,8 @@ class TrainStep:
             if evs:
                 evs[1].record(stream)
             n_b = geo.nwall * geo.nr
-            loss4, grad = mse(hist, self.target[p0:p1], self.gt_times, grad_scale=n_b / self.n_total, raw=True,
-                              irf=self.irf)
+            loss4, grad = fused_loss(hist, self.target[p0:p1], self.gt_times, grad_scale=n_b / self.n_total, raw=True,
+                                     irf=self.irf, kind=self.loss_kind, rate_floor=self.rate_floor)
             sums += loss4[2:4]
             if evs:
                 evs[2].record(stream)
@@ -431,8 +439,8 @@ class TrainStep:
         if ev:
             ev["fwd"][1].record(stream)
         hist, ws = out[0], (out[2] if cache else None)
-        loss4, grad = mse(hist, self.target, self.gt_times, grad_scale=self.n_local / self.n_total, raw=True,
-                          irf=self.irf)
+        loss4, grad = fused_loss(hist, self.target, self.gt_times, grad_scale=self.n_local / self.n_total, raw=True,
+                                 irf=self.irf, kind=self.loss_kind, rate_floor=self.rate_floor)
         loss2 = loss4[:2]
         if self.keep_grads:
             self.hist, self.grad_hist = hist, grad

@@ -1,11 +1,13 @@
 """Temporal-response timing at the C3 volume (128 x 128 wall points x 1024 bins) for IRFs of 1, 33, 129 and
 512 taps: (a) nlosgr_mse, the loss of an ideal detector; (b) nlosgr_mse_irf, the fused loss through the IRF;
 (c) the same loss and gradient composed from torch ops (conv1d, MSE, autograd.grad), what a user would write
-without (b).  Warm-up, timed repeats, device-event timing, one process; writes one JSON file and prints the
+without (b); (d) nlosgr_loss_irf with the Poisson deviance of photon counts in place of the MSE (rate_floor 1).
+Warm-up, timed repeats, device-event timing, one process; writes one JSON file and prints the
 markdown table of DESIGN §7.  (b) - (a) is also given as a share of the C3 training step
 (profiles/r06_c3_bench.json).
 
     python scripts/bench_irf.py [--out profiles/irf_c3.json] [--rows 16384] [--nr 1024] [--repeats 9]
+    python scripts/bench_irf.py --out profiles/loss_poisson_c3.json     # the record of column (d)
 """
 import argparse
 import json
@@ -18,6 +20,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from nlosgr.irf import IRF  # noqa: E402
+from nlosgr.loss import loss as fused_loss  # noqa: E402
 from nlosgr.train import mse  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -94,6 +97,9 @@ def main():
         irf = make_irf(L).to(DEV)
         e = {"center": irf.center}
         e["nlosgr_mse_irf"] = stats(timed(lambda: mse(hist, target, GT, raw=True, irf=irf), a.warmup, a.repeats))
+        e["nlosgr_loss_irf_poisson"] = stats(timed(lambda: fused_loss(hist, target, GT, raw=True, irf=irf, kind="poisson",
+                                                                      rate_floor=1.0), a.warmup, a.repeats))
+        e["poisson_extra_ms_over_mse_irf"] = e["nlosgr_loss_irf_poisson"]["median_ms"] - e["nlosgr_mse_irf"]["median_ms"]
         try:
             e["torch_conv1d_mse_autograd"] = stats(timed(lambda: torch_route(hist, target, irf), a.warmup, a.repeats))
             loss4, grad = mse(hist, target, GT, raw=True, irf=irf)
@@ -112,14 +118,16 @@ def main():
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)
         fh.write("\n")
-    print("| taps | nlosgr_mse (ms) | nlosgr_mse_irf (ms) | torch conv1d + MSE + autograd (ms) | (b) - (a) of the C3 step |")
-    print("|---|---|---|---|---|")
+    print("| taps | nlosgr_mse (ms) | nlosgr_mse_irf (ms) | torch conv1d + MSE + autograd (ms) | (b) - (a) of the C3 step "
+          "| nlosgr_loss_irf POISSON (ms) |")
+    print("|---|---|---|---|---|---|")
     for L in TAPS:
         e = res["taps"][str(L)]
         t = e["torch_conv1d_mse_autograd"]
         tt = f"{t['median_ms']:.2f}" if "median_ms" in t else "failed"
         sh = f"{100 * e['extra_share_of_c3_step']:.3f} %" if step_ms else "n/a"
-        print(f"| {L} | {base['median_ms']:.3f} | {e['nlosgr_mse_irf']['median_ms']:.3f} | {tt} | {sh} |")
+        print(f"| {L} | {base['median_ms']:.3f} | {e['nlosgr_mse_irf']['median_ms']:.3f} | {tt} | {sh} "
+              f"| {e['nlosgr_loss_irf_poisson']['median_ms']:.3f} |")
     worst = min((e.get("speedup_vs_torch", float("inf")) for e in res["taps"].values()))
     print(json.dumps({"metric": "nlosgr_mse_irf vs torch composition, worst speedup over the tap counts", "value": worst}))
 
