@@ -34,6 +34,8 @@
  *   nlosgr_backproject  no counterpart (the reference has no reconstruction from the capture itself): the
  *                          back-projection of the measured histograms onto the voxel grid, the baseline
  *                          reconstruction and a data-driven initial density
+ *   nlosgr_forward_project  no counterpart: the adjoint of the back-projection, voxel grid -> transients
+ *                          (checks a volume against the capture; the least-squares volume)
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -525,6 +527,64 @@ typedef struct nlosgr_backproject_opts {
 NLOSGR_API int nlosgr_backproject(const float* rows, const float* walls, int32_t nwall, int32_t nr,
                        const nlosgr_voxel_grid* grid, const nlosgr_backproject_opts* opt,
                        float* out, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Forward projection of a voxel grid (ABI 13, an addition): the transient every wall point of a confocal
+ * capture would measure from the volume, the adjoint of the back-projection above.  vol is [nx,ny,nz] in
+ * nlosgr_voxel_grid order, walls is [nwall][3], rows_out is [nwall][nr]; all device fp32.
+ * With d, u, k, f formed exactly as the back-projection forms them (same fp32 order, no contraction, the
+ * hardware square root), for voxel centre x and wall point i:
+ *   rows_i[j] = sum_x d^power vol(x) ((1-f) [k == j] + f [k+1 == j]),   0 <= j < nr.
+ * Both operators use the same fp32 coefficients, so <A v, h> = <v, A^T h> holds in exact summation for the
+ * powers 0..4 they share.  Negative powers are the physical falloff (-4: the confocal 1 / r^4); d^-p is
+ * 1 / d^p with d^p formed as the back-projection forms it.
+ * Contract:
+ *   1. No float atomics.  Every term is rounded once to the nearest multiple of a quantum q and added as a
+ *      64-bit integer (two's complement), so the result is bitwise repeatable and independent of nsplit, of
+ *      the launch shape and of the order workgroups run in.  A bin's integer sum is converted once:
+ *      int64 -> double, times q, -> fp32.  q = 2^(e - S) with
+ *        S  = 62 - ceil(log2(2 nvox)), nvox = nx ny nz;
+ *        e  = ev + ew;  max|vol| = m 2^ev with m in [0.5, 1) (frexp), found by a device reduction into the
+ *             workspace with no host synchronisation;  wmax = m' 2^ew likewise, where wmax is the host's
+ *             double-precision bound on the weight of every contributing pair:
+ *        wmax = R^|power| (|power| multiplications from 1.0; the reciprocal of that for power < 0) times
+ *             (1 + 2^-19), R = max(r0 + (nr + 1) dr, 0) for power >= 0 and R = r0 - 1.5 dr for power < 0,
+ *             dr = 1 / inv_dr in double.
+ *      So max|vol| wmax < 2^e, every term is below 2^S quanta and a bin's sum of at most nvox terms stays below
+ *      2^61.  q depends on (max|vol|, opts, nr, nvox) alone: a volume that is zero outside a sub-grid gives
+ *      bitwise the rows of the call on that sub-grid when ceil(log2(2 nvox)) is the same for both.
+ *   2. max|vol| == 0: zero rows.
+ *   3. Any non-finite voxel makes EVERY output row NaN (the back-projection poisons only the voxels that sample
+ *      a NaN bin; here the quantum cannot be formed, and a silent partial result would be worse).
+ *   4. nwall == 0 is valid and writes nothing.
+ *   5. nr > NLOSGR_IRF_MAX_NR: NLOSGR_E_UNSUPPORTED (the per-wall-point LDS row is 8 nr bytes).
+ *   6. Validated on the host before any launch (NLOSGR_E_INVALID): extents 1..1024, nr >= 1, nwall >= 0, power
+ *      -4..4, inv_dr finite and > 0, r0 finite, power < 0 only with r0 * inv_dr >= 2 (a pair contributes only
+ *      when u > -1, which then bounds d from below), nsplit >= 0, a finite wmax, null structs, tables and
+ *      pointers (walls / rows_out may be NULL only when nwall == 0).
+ *   7. No lane adds outside its row, whatever u is: u is clamped into [-2, nr + 1] (NaN to -2) and each add is
+ *      masked by its bin index.
+ * accumulate = 1 adds the call's rounded fp32 sum to rows_out: one more rounding per call (a volume projected
+ * as sub-grids or per rank); a non-finite voxel still writes NaN.
+ * A workgroup serves W wall points (the most of 4, 2, 1 that the wall has and whose rows fit 32 KiB of LDS) and
+ * one of nsplit parts of the voxels; nsplit = 0 lets the library choose (ceil(1024 / ceil(nwall / W)), at most
+ * one part per 1024 voxels), another value is forced (at most one part per 4 voxels).  Workspace: 256 bytes, plus
+ * 8 nwall nr when more than one part is used; the library neither allocates nor synchronises.
+ * ------------------------------------------------------------------------------------- */
+typedef struct nlosgr_forward_project_opts {
+    float   r0, inv_dr;  /* as nlosgr_backproject_opts */
+    int32_t power;       /* weight d^power, -4..4 */
+    int32_t accumulate;  /* 0: overwrite rows_out; 1: add this call's rounded sum */
+    int32_t nsplit;      /* voxel splits per wall point: 0 = chosen by the library, else forced (tests) */
+} nlosgr_forward_project_opts;
+
+/* Scratch bytes (host only; 0 with a message in nlosgr_last_error on the errors of contract 5 and 6). */
+NLOSGR_API size_t nlosgr_forward_project_workspace_bytes(int32_t nwall, int32_t nr, const nlosgr_voxel_grid* grid,
+                                              const nlosgr_forward_project_opts* opt);
+
+NLOSGR_API int nlosgr_forward_project(const float* vol, const float* walls, int32_t nwall, int32_t nr,
+                           const nlosgr_voxel_grid* grid, const nlosgr_forward_project_opts* opt,
+                           void* workspace, float* rows_out, void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

@@ -80,6 +80,11 @@ class BackprojectOpts(ctypes.Structure):
                 ("accumulate", ctypes.c_int32)]
 
 
+class ForwardProjectOpts(ctypes.Structure):
+    _fields_ = [("r0", ctypes.c_float), ("inv_dr", ctypes.c_float), ("power", ctypes.c_int32),
+                ("accumulate", ctypes.c_int32), ("nsplit", ctypes.c_int32)]
+
+
 ADAM_MAX_GROUPS = 8  # NLOSGR_ADAM_MAX_GROUPS
 MAX_PER_RAY = 256   # NLOSGR_MAX_PER_RAY
 IRF_MAX_TAPS = 512  # NLOSGR_IRF_MAX_TAPS
@@ -106,6 +111,7 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_loss_irf_workspace_bytes", "nlosgr_loss_irf",
            "nlosgr_carve_votes", "nlosgr_voxel_workspace_bytes", "nlosgr_voxelize", "nlosgr_volume_project",
            "nlosgr_mesh_workspace_bytes", "nlosgr_mesh_count", "nlosgr_mesh_emit", "nlosgr_backproject",
+           "nlosgr_forward_project_workspace_bytes", "nlosgr_forward_project",
            "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
@@ -183,6 +189,11 @@ def load():
     lib.nlosgr_backproject.argtypes = [_P, _P, ctypes.c_int32, ctypes.c_int32, PVG, ctypes.POINTER(BackprojectOpts),
                                        _P, _P]
     lib.nlosgr_backproject.restype = ctypes.c_int
+    PFP = ctypes.POINTER(ForwardProjectOpts)
+    lib.nlosgr_forward_project_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32, PVG, PFP]
+    lib.nlosgr_forward_project_workspace_bytes.restype = ctypes.c_size_t
+    lib.nlosgr_forward_project.argtypes = [_P, _P, ctypes.c_int32, ctypes.c_int32, PVG, PFP, _P, _P, _P]
+    lib.nlosgr_forward_project.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

@@ -1,0 +1,218 @@
+"""Forward projection of a voxel grid to the transients of a confocal capture, the adjoint of
+nlosgr.backproject, and what it makes possible: checking a volume against the capture, and the least-squares
+volume (Landweber iteration).  For voxel centre x and wall point i (include/nlosgr.h, ABI 13):
+
+    d = |x - wall_i|,  u = (d - r0) / dr,  k = floor(u),  f = u - k
+    rows_i[j] = sum_x d^power vol(x) ((1-f) [k == j] + f [k+1 == j]),   0 <= j < nr
+
+with d, u, k, f the fp32 values nlosgr_backproject forms, so <A v, h> = <v, A^T h> for powers 0..4.  One HIP
+pass (nlosgr_forward_project: a workgroup per wall point and voxel split, 64-bit fixed-point adds into an LDS
+row, no float atomics): bitwise repeatable and independent of the split.  A non-finite voxel makes every row
+NaN.  Negative powers are the physical falloff; they need r0 >= 2 dr.  No CPU fallback, no backward.
+
+    python -m nlosgr.forward_project CAPTURE.mat --resolution R --start S --end E [--power P] [--iterations N]
+        --out lw.npz [--mesh lw.ply --level-frac F]
+"""
+import argparse
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .backproject import _gpu_f32, backproject, fp32_window
+from .voxelize import VoxelGrid, front_view
+
+
+@torch.no_grad()
+def forward_project(volume, walls, grid, r0, dr, nr, power=0, out=None, accumulate=False, nsplit=0):
+    """[nwall, nr] fp32 (the layout data.volume_target returns): the transients of volume [nx, ny, nz] on `grid`
+    (voxelize.VoxelGrid) at walls [nwall, 3].  r0: radius of bin 0; dr: bin width; power -4..4: weight d^power.
+    out: an [nwall, nr] tensor to write (accumulate=False) or to add this call's rounded sum to
+    (accumulate=True: a volume projected as sub-grids or per rank).  nsplit: voxel splits per wall point, 0 = the
+    library's choice; the result does not depend on it."""
+    lib = _lib.load()
+    volume, walls = _gpu_f32(volume, "forward_project"), _gpu_f32(walls, "forward_project")
+    if not isinstance(grid, VoxelGrid):
+        raise TypeError("nlosgr: grid must be a voxelize.VoxelGrid")
+    shape = grid.shape
+    if tuple(volume.shape) != shape or walls.dim() != 2 or walls.shape[1] != 3:
+        raise ValueError(f"nlosgr: forward_project takes a volume {shape} (the grid's shape) and walls [nwall, 3]")
+    dev = volume.device
+    if walls.device != dev:
+        raise ValueError(f"nlosgr: walls must be on {dev}")
+    nwall, nr = int(walls.shape[0]), int(nr)
+    if nr < 1:
+        raise ValueError("nlosgr: nr must be >= 1")
+    if out is None:
+        if accumulate:
+            raise ValueError("nlosgr: accumulate=True needs the rows to add to (out=)")
+        out = torch.empty((nwall, nr), device=dev)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+            raise RuntimeError("nlosgr: forward_project needs float32 GPU tensors (no CPU fallback)")
+        if tuple(out.shape) != (nwall, nr) or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"nlosgr: out must be a contiguous {(nwall, nr)} tensor on {dev}")
+    if not float(dr) > 0:
+        raise ValueError("nlosgr: dr must be > 0")
+    xs, ys, zs = grid.on(dev)
+    vg = _lib.VoxelGrid(shape[0], shape[1], shape[2], _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(zs))
+    opt = _lib.ForwardProjectOpts(*fp32_window(r0, dr), int(power), int(bool(accumulate)), int(nsplit))
+    nbytes = lib.nlosgr_forward_project_workspace_bytes(nwall, nr, ctypes.byref(vg), ctypes.byref(opt))
+    if nbytes == 0:
+        raise RuntimeError("nlosgr error: " + lib.nlosgr_last_error().decode(errors="replace"))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.nlosgr_forward_project(_lib.ptr(volume), _lib.ptr(walls), nwall, nr, ctypes.byref(vg),
+                                          ctypes.byref(opt), _lib.ptr(ws), _lib.ptr(out), _lib.stream_handle(dev)))
+    return out
+
+
+def _spacing(t):
+    n = int(t.shape[0])
+    if n < 2:
+        raise ValueError("nlosgr: a voxel volume needs at least two centres per axis")
+    return (float(t[-1]) - float(t[0])) / (n - 1)
+
+
+@torch.no_grad()
+def voxel_transient(volume, grid, walls, r, c_deltaT, y):
+    """[nwall, nr]: the histogram the Gaussian renderer (no occlusion) produces for a volume holding
+    density x albedo (what voxelize returns as `albedo`), on the renderer's radial table r [nr] (geometry.r).
+    The renderer's bin is Y^2 c deltaT  integral rho sin(theta) / r^2 dtheta dphi, and dV = r^2 sin(theta) dr dtheta
+    dphi, so with dr = (r[-1] - r[0]) / (nr - 1) the table's spacing (a linspace over nr points: not c deltaT) and
+    dV the product of the grid's table spacings:
+
+        y^2 (c_deltaT / dr) dV A_-4(volume),   r0 = r[0]
+
+    y: volume_position[1], the renderer's Y."""
+    r = torch.as_tensor(r).detach().double().cpu()
+    nr = int(r.shape[0])
+    if nr < 2:
+        raise ValueError("nlosgr: voxel_transient needs a radial table of at least two bins")
+    r0, dr = float(r[0]), (float(r[-1]) - float(r[0])) / (nr - 1)
+    dv = _spacing(grid.xs) * _spacing(grid.ys) * _spacing(grid.zs)
+    rows = forward_project(volume, walls, grid, r0, dr, nr, power=-4)
+    return rows.mul_(float(y) ** 2 * (float(c_deltaT) / dr) * dv)
+
+
+@torch.no_grad()
+def operator_norm(walls, grid, r0, dr, nr, power=0, iterations=8):
+    """The largest eigenvalue of A^T A (A = forward_project with this window and power 0..4) by power iteration
+    from the all-ones volume: a float, one host read at the end.  1 / operator_norm is the Landweber step."""
+    walls = _gpu_f32(walls, "operator_norm")
+    if not isinstance(grid, VoxelGrid):
+        raise TypeError("nlosgr: grid must be a voxelize.VoxelGrid")
+    if int(iterations) < 1:
+        raise ValueError("nlosgr: iterations must be >= 1")
+    v = torch.ones(grid.shape, device=walls.device)
+    lam = None
+    for _ in range(int(iterations)):
+        v = v / v.double().norm().float()
+        w = backproject(forward_project(v, walls, grid, r0, dr, nr, power=power), walls, grid, r0, dr, power=power)
+        lam = w.double().norm()
+        v = w
+    return float(lam)
+
+
+@torch.no_grad()
+def landweber(rows, walls, grid, r0, dr, power=0, iterations=30, nonneg=True, step=None, x0=None):
+    """(volume [nx, ny, nz], objective [iterations]): projected gradient on 1/2 |A v - h|^2,
+    v <- max(v - step A^T (A v - h), 0) from x0 (zeros by default), step = 1 / operator_norm by default, power
+    0..4 (the range of A^T; for the falloff scale the rows by r^q first, as the back-projection's users do).
+    objective[n] is 1/2 |A v - h|^2 BEFORE update n, a device tensor (no host read inside the loop)."""
+    rows, walls = _gpu_f32(rows, "landweber"), _gpu_f32(walls, "landweber")
+    if rows.dim() != 2 or walls.dim() != 2 or walls.shape[1] != 3 or walls.shape[0] != rows.shape[0]:
+        raise ValueError("nlosgr: landweber takes rows [nwall, nr] and walls [nwall, 3]")
+    if not isinstance(grid, VoxelGrid):
+        raise TypeError("nlosgr: grid must be a voxelize.VoxelGrid")
+    if not 0 <= int(power) <= 4:
+        raise ValueError("nlosgr: landweber takes a power in 0..4 (the range of backproject)")
+    nr = int(rows.shape[1])
+    if step is None:
+        step = 1.0 / operator_norm(walls, grid, r0, dr, nr, power=power)
+    step = float(step)
+    if x0 is None:
+        v = torch.zeros(grid.shape, device=rows.device)
+    else:
+        v = _gpu_f32(x0, "landweber").clone()
+        if tuple(v.shape) != grid.shape:
+            raise ValueError(f"nlosgr: x0 must have the grid's shape {grid.shape}")
+    objective = torch.zeros(int(iterations), dtype=torch.float64, device=rows.device)
+    res = torch.empty_like(rows)
+    for n in range(int(iterations)):
+        forward_project(v, walls, grid, r0, dr, nr, power=power, out=res)
+        res.sub_(rows)
+        objective[n] = 0.5 * res.double().square().sum()
+        v.sub_(backproject(res, walls, grid, r0, dr, power=power), alpha=step)
+        if nonneg:
+            v.clamp_(min=0.0)
+    return v, objective
+
+
+@torch.no_grad()
+def landweber_capture(data_kwargs, resolution, start, end, power=0, iterations=30):
+    """Landweber on the capture in data_kwargs (data.make_data_kwargs) over bins [floor(start), floor(start) +
+    end - start) onto VoxelGrid(volume_position, volume_size, resolution), as backproject_capture lays it out.
+    Returns {"volume", "objective", "front", "depth", "grid"}."""
+    from .data import volume_target
+    I1 = int(np.floor(start))
+    rows = _gpu_f32(volume_target(data_kwargs, start, int(end - start)), "landweber_capture")
+    walls = data_kwargs["camera_grid_positions"].t().contiguous().float()
+    vp = data_kwargs["volume_position"]
+    grid = VoxelGrid([float(v) for v in vp], float(data_kwargs["volume_size"]), resolution)
+    cdt = float(data_kwargs["c"]) * float(data_kwargs["deltaT"])
+    vol, obj = landweber(rows, walls, grid, I1 * cdt, cdt, power=power, iterations=iterations)
+    front, depth = front_view(vol, grid)
+    return {"volume": vol, "objective": obj, "front": front, "depth": depth, "grid": grid}
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m nlosgr.forward_project",
+                                 description="Least-squares voxel volume of a confocal capture (Landweber iteration "
+                                             "with the forward projector and the back-projection).")
+    ap.add_argument("capture", help="Zaragoza-format .mat file")
+    ap.add_argument("--resolution", type=int, default=64)
+    ap.add_argument("--start", type=int, required=True, help="first time bin")
+    ap.add_argument("--end", type=int, required=True, help="one past the last time bin")
+    ap.add_argument("--power", type=int, default=0, choices=range(5), help="weight d^power of the operator")
+    ap.add_argument("--iterations", type=int, default=30)
+    ap.add_argument("--out", default="lw.npz")
+    ap.add_argument("--mesh", default=None, help="also write the isosurface as a PLY file")
+    ap.add_argument("--level-frac", type=float, default=0.5, help="isosurface level as a fraction of the maximum")
+    a = ap.parse_args(argv)
+    if a.end <= a.start:
+        ap.error("--end must be greater than --start")
+    if a.iterations < 1:
+        ap.error("--iterations must be >= 1")
+    if a.resolution < 2:
+        ap.error("--resolution must be >= 2")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from .data import make_data_kwargs
+    if not torch.cuda.is_available():
+        raise RuntimeError("nlosgr: forward_project needs a GPU (no CPU fallback)")
+    dev = torch.device("cuda:0")
+    dk, *_ = make_data_kwargs(a.capture, dev, shuffle=False)
+    out = landweber_capture(dk, a.resolution, a.start, a.end, power=a.power, iterations=a.iterations)
+    grid, vol = out["grid"], out["volume"]
+    obj = out["objective"].cpu().numpy()
+    vp = dk["volume_position"].cpu().numpy().astype(np.float32)
+    # the key names of python -m nlosgr.backproject, plus the objective per iteration
+    np.savez_compressed(a.out, density=vol.cpu().numpy(), albedo=vol.cpu().numpy(), front=out["front"].cpu().numpy(),
+                        depth=out["depth"].cpu().numpy(), xs=grid.xs.numpy(), ys=grid.ys.numpy(), zs=grid.zs.numpy(),
+                        cam=np.array([vp[0], 0.0, vp[2]], dtype=np.float32), objective=obj)
+    print(f"wrote {a.out}: {grid.shape} voxels, {dk['camera_grid_positions'].shape[1]} wall points, bins "
+          f"[{a.start}, {a.end}), power {a.power}, {a.iterations} iterations, objective {obj[0]:.6g} -> {obj[-1]:.6g}")
+    if a.mesh:
+        from .mesh import isosurface, write_ply
+        level = a.level_frac * float(vol.max())
+        mesh = isosurface(vol, grid, level)
+        write_ply(a.mesh, mesh)
+        print(f"wrote {a.mesh}: level {level:.6g}, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles")
+
+
+if __name__ == "__main__":
+    main()
