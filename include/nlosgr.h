@@ -36,6 +36,8 @@
  *                          reconstruction and a data-driven initial density
  *   nlosgr_forward_project  no counterpart: the adjoint of the back-projection, voxel grid -> transients
  *                          (checks a volume against the capture; the least-squares volume)
+ *   nlosgr_*_nc         no counterpart: the two voxel operators for a non-confocal capture (laser spot and
+ *                          sensed spot differ); the Gaussian renderer itself stays confocal
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -585,6 +587,52 @@ NLOSGR_API size_t nlosgr_forward_project_workspace_bytes(int32_t nwall, int32_t 
 NLOSGR_API int nlosgr_forward_project(const float* vol, const float* walls, int32_t nwall, int32_t nr,
                            const nlosgr_voxel_grid* grid, const nlosgr_forward_project_opts* opt,
                            void* workspace, float* rows_out, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Non-confocal back-projection and forward projection (ABI 13, additions): measurement i is sensed at wall
+ * point s_i (sensors [nmeas][3], what the confocal entry points call walls) while the laser lights wall point
+ * l_i (lasers [nlaser][3]; nlaser == nmeas: one spot per measurement, nlaser == 1: one spot for the whole
+ * capture).  Light of voxel x travels |x - l_i| + |x - s_i|, and the rows' bins hold HALF that path: r0 is the
+ * radius of bin 0 and 1 / inv_dr = c deltaT the bin width in half-path units, as in a confocal capture.
+ * For voxel centre x and measurement i, all fp32, no contraction, the hardware square root:
+ *   ds = |x - s_i|, dl = |x - l_i|, each formed as the confocal d: sqrt((dx*dx + dy*dy) + dz*dz).
+ *   g = 0.5f * (dl + ds): half the path.  m = dl * ds.
+ *   u = (g - r0) * inv_dr, k = floor(u), f = u - k; clamps and masks as the confocal kernels.
+ *   weight = m^(power/2): 0: 1; 1: sqrt(m); 2: m; 3: m * sqrt(m); 4: m * m; a negative power: 1 / that
+ *     (-4 is the physical 1 / (dl^2 ds^2)).
+ *   back-projection:     out(x)    = sum_i weight ((1-f) h_i[k] + f h_i[k+1])
+ *   forward projection:  rows_i[j] = sum_x weight vol(x) ((1-f) [k == j] + f [k+1 == j])
+ * With l_i == s_i: g == d and m == d*d exactly, so the even powers give the confocal entry points' results bit
+ * for bit; the odd powers differ by the rounding of sqrt(d*d) against d.  nlaser == 1 gives bitwise the result of
+ * the same spot repeated nmeas times (the laser distance is then formed once per voxel, not once per pair).
+ * The contracts of the confocal entry points carry over unchanged:
+ *   back-projection: measurements in ascending order, tiles of 256 counted from measurement 0, an fp32 sum
+ *     within a tile, an fp64 sum across tiles, one rounding to fp32; accumulate, NaN bins and nmeas == 0 as there.
+ *     Validated as there (power 0..4), plus nlaser in {1, nmeas} and a null lasers pointer.
+ *   forward projection: contracts 1..7 of the forward-projection block above (64-bit fixed-point adds, no float
+ *     atomics, independent of nsplit and launch shape, a non-finite voxel makes every row NaN, nmeas == 0 writes
+ *     nothing, nr > NLOSGR_IRF_MAX_NR is NLOSGR_E_UNSUPPORTED, no add outside a row), the same workspace
+ *     layout and size, with two changes to the quantum's wmax:
+ *       power >= 0: unchanged, R = max(r0 + (nr + 1) dr, 0): m <= g^2 (AM-GM), and g is inside the window.
+ *       power <  0: the window does not bound m from below (a voxel may sit next to the laser while far from
+ *         the sensor), so the caller passes dmin: a pair with min(dl, ds) < dmin contributes nothing, and
+ *         wmax is formed with R = dmin.  dmin must be finite and > 0 (NLOSGR_E_INVALID otherwise); the confocal
+ *         rule r0 * inv_dr >= 2 is not required.  dmin is ignored for power >= 0.
+ *     Validated as there, plus nlaser in {1, nmeas}, a null lasers pointer and the dmin rule.
+ * ------------------------------------------------------------------------------------- */
+NLOSGR_API int nlosgr_backproject_nc(const float* rows, const float* sensors, const float* lasers, int32_t nlaser,
+                          int32_t nmeas, int32_t nr, const nlosgr_voxel_grid* grid,
+                          const nlosgr_backproject_opts* opt, float* out, void* hip_stream);
+
+/* Scratch bytes (host only; 0 with a message in nlosgr_last_error on a validation error). */
+NLOSGR_API size_t nlosgr_forward_project_nc_workspace_bytes(int32_t nlaser, int32_t nmeas, int32_t nr,
+                                                 const nlosgr_voxel_grid* grid,
+                                                 const nlosgr_forward_project_opts* opt, float dmin);
+
+NLOSGR_API int nlosgr_forward_project_nc(const float* vol, const float* sensors, const float* lasers, int32_t nlaser,
+                              int32_t nmeas, int32_t nr, const nlosgr_voxel_grid* grid,
+                              const nlosgr_forward_project_opts* opt, float dmin, void* workspace,
+                              float* rows_out, void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

@@ -20,20 +20,12 @@
 // v_sqrt_f32 (__builtin_amdgcn_sqrtf, 1 ulp): parity is judged against float64, not torch bit-exactness.
 // A pair's two bins come from one 8-byte read clamped into the row (a one-bin row: its bin alone) and the values
 // that are not the pair's bins are dropped by selects, so no lane ever reads outside its row, whatever u is.
-#include "nlosgr_common.hpp"
+#include "nlosgr_project.hpp"
 
 using namespace nlosgr;
 using namespace nlosgr::detail;
 
 namespace {
-
-constexpr int kBpTile = 256;     // wall points per LDS tile (the summation contract's tile)
-constexpr int kBpBrick = 8;      // brick edge (voxels)
-constexpr int kBpGroup = 4;      // wall points whose bin reads a lane keeps in flight together
-constexpr int kBpMaxExtent = 1024;
-
-static_assert(kBpTile == kBlock, "one wall point per thread when a tile is staged");
-static_assert(kBpBrick * kBpBrick * kBpBrick == 2 * kBlock, "two voxels per lane");
 
 struct BpArgs {
     const float* rows;
@@ -57,20 +49,7 @@ __device__ __forceinline__ float bp_weight(float d) {
     return d2 * d2;
 }
 
-// one (voxel, wall point) pair before its bins are read.  Both bins come from ONE 8-byte read at bin
-// kb = clamp(k, 0, nr - 2) (4-byte aligned, always inside the row), which halves the gather's memory
-// instructions; e = k - kb says which of the two values are the pair's bins: 0: (h[k], h[k+1]) = (x, y);
-// -1 (k = -1): (0, x);  1 (k = nr - 1): (y, 0);  anything else: both outside the row
-struct BpTap {
-    unsigned ib;   // byte offset of bin kb into the row
-    int e;
-    float f, w;    // f, d^POWER
-};
-
-struct __attribute__((packed, aligned(4))) BpBins {
-    float x, y;
-};
-
+// one (voxel, wall point) pair as a BpTap (nlosgr_project.hpp: the two-bin read and its selects)
 // ss = dx*dx + dy*dy (shared by the lane's two voxels); kmax = max(nr - 2, 0)
 template <int POWER>
 __device__ __forceinline__ BpTap bp_tap(float ss, float dz, float r0, float inv_dr, int kmax, float umax) {
@@ -87,26 +66,6 @@ __device__ __forceinline__ BpTap bp_tap(float ss, float dz, float r0, float inv_
     t.ib = 4u * (unsigned)kb;
     t.e = k - kb;
     return t;
-}
-
-// d^POWER * ((1-f) h[k] + f h[k+1]); a value that is not one of the pair's bins is dropped by a select, so
-// its NaN does not leak
-template <int POWER>
-__device__ __forceinline__ float bp_eval(const BpTap& t, const BpBins v) {
-    const float h0 = t.e == 0 ? v.x : (t.e == 1 ? v.y : 0.0f);
-    const float h1 = t.e == 0 ? v.y : (t.e == -1 ? v.x : 0.0f);
-    const float s = fmaf(t.f, h1, (1.0f - t.f) * h0);
-    return POWER == 0 ? s : t.w * s;
-}
-
-// PAIR: rows of two or more bins, one 8-byte read; a one-bin row reads its bin alone (y = 0: bin 1 is outside)
-template <bool PAIR>
-__device__ __forceinline__ BpBins bp_read(const char* r, unsigned ib) {
-    if (PAIR) return *(const BpBins*)(r + ib);
-    BpBins v;
-    v.x = *(const float*)r;
-    v.y = 0.0f;
-    return v;
 }
 
 // wall points [j, j + N) of the staged tile: every bin offset first, then all 2 N reads, then the sums in

@@ -24,20 +24,12 @@
 // [-2, nr + 1], and an add into bin j = k or k + 1 is issued only under (unsigned)j < nr.  Voxel indices stay
 // below the split's end <= nvox, and (ix, iy, iz) is the mixed-radix form of such an index, so every table read
 // is inside its table.
-#include "nlosgr_common.hpp"
+#include "nlosgr_project.hpp"
 
 using namespace nlosgr;
 using namespace nlosgr::detail;
 
 namespace {
-
-constexpr int kFpRun = 4;                  // voxels adjacent in z that one lane owns per step
-constexpr int kFpStep = kFpRun * kBlock;   // voxels a workgroup covers per step
-constexpr int kFpMaxExtent = 1024;
-constexpr int kFpHeader = 256;             // workspace: [0] the bits of max|vol|; the int64 rows start here
-constexpr unsigned kFpTargetGroups = 1024; // the library's nsplit fills 256 CUs four times over
-constexpr size_t kFpRowBytes = 32768;      // LDS rows of a workgroup that serves more than one wall point
-constexpr double kFpWeightMargin = 1.0 + 1.0 / 524288.0;   // 1 + 2^-19: fp32 error of d^power at the window's end
 
 struct FpArgs {
     const float* vol;
@@ -64,14 +56,6 @@ __device__ __forceinline__ float fp_weight(float d) {
     return POWER < 0 ? 1.0f / p : p;
 }
 
-// scale 2^(S - e) of a term to quanta and 2^(e - S) back, e = ev + ew with max|vol| = m 2^ev, m in [0.5, 1)
-__device__ __forceinline__ void fp_unit(unsigned vbits, int ew, int S, double& to_q, double& from_q) {
-    int ev;
-    (void)frexp((double)__uint_as_float(vbits), &ev);
-    to_q = ldexp(1.0, S - (ev + ew));
-    from_q = ldexp(1.0, (ev + ew) - S);
-}
-
 // timing-only builds (their rows are wrong): 1 = no LDS adds (the values go into a register sum that is kept
 // alive), 2 = no fp32 -> int64 conversion (a bit cast in its place)
 #ifndef NLOSGR_FP_TIMING
@@ -89,14 +73,6 @@ __device__ __forceinline__ void fp_add(unsigned long long* row, int j, int nr, l
 __device__ __forceinline__ long long fp_quanta(float term, double to_q) {
     if (NLOSGR_FP_TIMING == 2) return (long long)__float_as_int(term);
     return __double2ll_rn((double)term * to_q);
-}
-
-__global__ __launch_bounds__(kBlock) void fp_vmax_kernel(const float* __restrict__ vol, unsigned n, unsigned* out) {
-    unsigned m = 0u;
-    for (unsigned i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock)
-        m = max(m, __float_as_uint(vol[i]) & 0x7fffffffu);      // |v| as bits: ordered as the values, NaN on top
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if (lane_id() == 0 && m) atomicMax(out, m);
 }
 
 template <int POWER, bool MERGE, int W>
@@ -210,41 +186,6 @@ __global__ __launch_bounds__(kBlock) void forward_project_kernel(FpArgs a) {
     }
 }
 
-// nsplit > 1: the int64 sums of every (wall point, bin) to floats
-__global__ __launch_bounds__(kBlock) void fp_finish_kernel(const unsigned long long* __restrict__ acc, size_t n,
-                                                           const unsigned* vmax, int ew, int S, int accumulate,
-                                                           float* out) {
-    const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= n) return;
-    const unsigned vb = *vmax;
-    float r;
-    if (vb >= 0x7f800000u) {
-        r = __uint_as_float(0x7fc00000u);
-    } else {
-        double to_q, from_q;
-        fp_unit(vb, ew, S, to_q, from_q);
-        r = (float)((double)(long long)acc[j] * from_q);
-    }
-    out[j] = accumulate && vb < 0x7f800000u ? out[j] + r : r;
-}
-
-int fp_ceil_log2(unsigned long long v) {      // the least b with v <= 2^b
-    int b = 0;
-    while ((1ull << b) < v) ++b;
-    return b;
-}
-
-// wall points per workgroup: the most of 4, 2, 1 that the wall has and whose rows fit kFpRowBytes of LDS
-int fp_walls_per_group(int nwall, int nr) {
-#ifdef NLOSGR_FP_ONEWALL
-    return 1;                          // A/B build: every workgroup walks the volume for one wall point
-#else
-    int w = 4;
-    while (w > 1 && (w > nwall || (size_t)w * nr * sizeof(unsigned long long) > kFpRowBytes)) w >>= 1;
-    return w;
-#endif
-}
-
 // host validation shared by both entry points; on success the weight bound's exponent and the split count
 int fp_plan(int32_t nwall, int32_t nr, const nlosgr_voxel_grid* grid, const nlosgr_forward_project_opts* opt, int* ew,
             int* nsplit) {
@@ -275,18 +216,7 @@ int fp_plan(int32_t nwall, int32_t nr, const nlosgr_voxel_grid* grid, const nlos
     w *= kFpWeightMargin;
     if (!(w <= 1.0e300)) return set_err(NLOSGR_E_INVALID, "r0 and inv_dr give no finite bound on d^power");
     (void)frexp(w, ew);
-    const unsigned nvox = (unsigned)grid->nx * grid->ny * grid->nz;
-    // the library's choice: no split below one step of a workgroup; a forced count: no split below one lane's run
-    const unsigned most = opt->nsplit ? (nvox + kFpRun - 1) / kFpRun : (nvox + kFpStep - 1) / kFpStep;
-    const int W = fp_walls_per_group(nwall, nr);
-    const unsigned groups = nwall > 0 ? (unsigned)((nwall + W - 1) / W) : 1u;
-    unsigned ns = opt->nsplit ? (unsigned)opt->nsplit : (kFpTargetGroups + groups - 1) / groups;
-    if (ns > most) ns = most;
-    if (ns < 1) ns = 1;
-    if ((unsigned long long)ns * groups > 0x7fffffffull)
-        return set_err(NLOSGR_E_UNSUPPORTED, "workgroups * nsplit above 2^31 - 1");
-    *nsplit = (int)ns;
-    return NLOSGR_OK;
+    return fp_split_count(nwall, nr, grid, opt->nsplit, nsplit);
 }
 
 }  // namespace

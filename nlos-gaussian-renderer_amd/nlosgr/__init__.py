@@ -16,6 +16,7 @@ Layers:
     nlosgr.mesh            surface output: isosurface of a voxelized field as a triangle mesh, PLY export
     nlosgr.backproject     the capture on a voxel grid: back-projection, time filters, backproject_capture
     nlosgr.forward_project its adjoint: voxel grid -> transients, voxel_transient, operator_norm, landweber
+                           (both take lasers= for a non-confocal capture: the laser spot differs from the sensed one)
     nlosgr.irf             temporal instrument response: IRF, gaussian_irf, convolve_time (render -> capture)
     nlosgr.loss            photon-count likelihood: fused loss(kind=), PoissonDeviance, simulate_capture
 """

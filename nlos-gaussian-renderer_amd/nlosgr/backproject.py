@@ -15,6 +15,11 @@ write_ply.  Filtered back-projection filters the rows along time first, through 
 
     backproject(irf_apply(rows, time_filter("log", sigma_bins=2.0)), walls, grid, r0, dr)
 
+A non-confocal capture (the laser lights another wall point than the one sensed; `lasers=`) replaces d by half
+the path, g = (|x - laser_i| + |x - wall_i|) / 2, and d^2 by m = |x - laser_i| |x - wall_i| (weight m^(power/2)),
+through nlosgr_backproject_nc; with lasers == walls that is the confocal result.  In either kind of file deltaT is
+the bin width in HALF-path units: bin j of a row holds the light whose whole path is 2 (r0 + j c deltaT).
+
 No CPU fallback, no backward.
 
     python -m nlosgr.backproject CAPTURE.mat --resolution 128 --start S --end E [--power P]
@@ -40,6 +45,23 @@ def _gpu_f32(t, what):
     return t.detach().contiguous()
 
 
+def _lasers_arg(lasers, walls, what):
+    """lasers= of the voxel operators: a float32 [nmeas, 3] or [1, 3] tensor on the walls' device."""
+    lasers = _gpu_f32(lasers, what)
+    if lasers.dim() != 2 or lasers.shape[1] != 3 or int(lasers.shape[0]) not in (1, int(walls.shape[0])):
+        raise ValueError(f"nlosgr: lasers must be [{int(walls.shape[0])}, 3] (one per measurement) or [1, 3]")
+    if lasers.device != walls.device:
+        raise ValueError(f"nlosgr: lasers must be on {walls.device}")
+    return lasers
+
+
+def capture_lasers(data_kwargs):
+    """[nmeas, 3] or [1, 3] laser spots of a capture's data_kwargs (data.make_data_kwargs), or None for a
+    confocal capture (no "laser_grid_positions" key)."""
+    lasers = data_kwargs.get("laser_grid_positions")
+    return None if lasers is None else lasers.t().contiguous().float()
+
+
 def fp32_window(r0, dr):
     """(r0, inv_dr) as the fp32 values nlosgr_backproject computes with: r0 rounded to fp32 and the fp32
     quotient 1 / dr (a float64 check of a result has to start from these two)."""
@@ -47,16 +69,20 @@ def fp32_window(r0, dr):
 
 
 @torch.no_grad()
-def backproject(rows, walls, grid, r0, dr, power=0, out=None, accumulate=False):
+def backproject(rows, walls, grid, r0, dr, power=0, out=None, accumulate=False, lasers=None):
     """[nx, ny, nz] fp32: the back-projection of rows [nwall, nr] (the layout data.volume_target returns)
     measured at walls [nwall, 3] onto `grid` (voxelize.VoxelGrid).  r0: radius of bin 0; dr: bin width;
     power 0..4: weight d^power (falloff compensation).  out: an [nx, ny, nz] tensor to write (accumulate=False)
     or to add this call's sum to (accumulate=True: a wall back-projected in batches or per rank; one more
-    rounding per call, so close to, not bitwise equal to, one call)."""
+    rounding per call, so close to, not bitwise equal to, one call).  lasers: None for a confocal capture;
+    else the laser spots [nwall, 3], or [1, 3] for one spot, of a non-confocal capture whose walls are the sensed
+    points (r0 and dr then count half the path, the weight is (|x - laser| |x - wall|)^(power/2))."""
     lib = _lib.load()
     rows, walls = _gpu_f32(rows, "backproject"), _gpu_f32(walls, "backproject")
     if rows.dim() != 2 or walls.dim() != 2 or walls.shape[1] != 3 or walls.shape[0] != rows.shape[0]:
         raise ValueError("nlosgr: backproject takes rows [nwall, nr] and walls [nwall, 3]")
+    if lasers is not None:
+        lasers = _lasers_arg(lasers, walls, "backproject")
     if not isinstance(grid, VoxelGrid):
         raise TypeError("nlosgr: grid must be a voxelize.VoxelGrid")
     dev = rows.device
@@ -75,8 +101,13 @@ def backproject(rows, walls, grid, r0, dr, power=0, out=None, accumulate=False):
     xs, ys, zs = grid.on(dev)
     vg = _lib.VoxelGrid(shape[0], shape[1], shape[2], _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(zs))
     opt = _lib.BackprojectOpts(*fp32_window(r0, dr), int(power), int(bool(accumulate)))
-    _lib.check(lib.nlosgr_backproject(_lib.ptr(rows), _lib.ptr(walls), rows.shape[0], rows.shape[1], ctypes.byref(vg),
-                                      ctypes.byref(opt), _lib.ptr(out), _lib.stream_handle(dev)))
+    if lasers is None:
+        _lib.check(lib.nlosgr_backproject(_lib.ptr(rows), _lib.ptr(walls), rows.shape[0], rows.shape[1],
+                                          ctypes.byref(vg), ctypes.byref(opt), _lib.ptr(out), _lib.stream_handle(dev)))
+    else:
+        _lib.check(lib.nlosgr_backproject_nc(_lib.ptr(rows), _lib.ptr(walls), _lib.ptr(lasers), lasers.shape[0],
+                                             rows.shape[0], rows.shape[1], ctypes.byref(vg), ctypes.byref(opt),
+                                             _lib.ptr(out), _lib.stream_handle(dev)))
     return out
 
 
@@ -103,7 +134,8 @@ def backproject_capture(data_kwargs, resolution, start, end, power=0, filter="lo
     """Back-projection of the capture in data_kwargs (data.make_data_kwargs: the shuffled wall order is the
     order of both the rows and the wall points) over bins [floor(start), floor(start) + end - start) onto
     VoxelGrid(volume_position, volume_size, resolution).  filter: "none", "laplacian" or "log" (time_filter);
-    positive: clamp at zero.  Returns {"volume" [nx,ny,nz], "front", "depth" (voxelize.front_view), "grid"}."""
+    positive: clamp at zero.  A non-confocal capture (data_kwargs["laser_grid_positions"]) is back-projected with
+    its laser spots.  Returns {"volume" [nx,ny,nz], "front", "depth" (voxelize.front_view), "grid"}."""
     from .data import volume_target
     if filter not in FILTERS:
         raise ValueError(f"nlosgr: filter must be one of {FILTERS}")
@@ -115,7 +147,7 @@ def backproject_capture(data_kwargs, resolution, start, end, power=0, filter="lo
     vp = data_kwargs["volume_position"]
     grid = VoxelGrid([float(v) for v in vp], float(data_kwargs["volume_size"]), resolution)
     cdt = float(data_kwargs["c"]) * float(data_kwargs["deltaT"])
-    vol = backproject(rows, walls, grid, I1 * cdt, cdt, power=power)
+    vol = backproject(rows, walls, grid, I1 * cdt, cdt, power=power, lasers=capture_lasers(data_kwargs))
     if positive:
         vol.clamp_(min=0.0)
     front, depth = front_view(vol, grid)
@@ -124,7 +156,8 @@ def backproject_capture(data_kwargs, resolution, start, end, power=0, filter="lo
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m nlosgr.backproject",
-                                 description="Back-project a confocal capture onto a voxel grid (volume, front view, depth).")
+                                 description="Back-project a confocal or non-confocal capture (the optional field "
+                                             "laserGridPositions) onto a voxel grid (volume, front view, depth).")
     ap.add_argument("capture", help="Zaragoza-format .mat file")
     ap.add_argument("--resolution", type=int, default=128)
     ap.add_argument("--start", type=int, required=True, help="first time bin")

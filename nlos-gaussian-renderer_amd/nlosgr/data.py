@@ -11,6 +11,13 @@ with `data` [T, H, W] (optionally with leading singleton axes), `cameraPosition`
 same order (main.py:93). No captured file ships with the reference, so the format is pinned only
 by that call site (parity unpinned; tests/test_data_cpu.py round-trips a synthetic file).
 MATLAB v7.3 (HDF5) files need h5py, which this image lacks: they raise with that message.
+
+A non-confocal capture (the laser lights another wall point than the one sensed) carries the optional field
+`laserGridPositions`, [3, H*W] (one laser spot per sensed point) or [3, 1] (one spot for the whole capture);
+`cameraGridPositions` are then the sensed points.  In both kinds of file `deltaT` is the bin width in HALF-path
+units: bin j holds the light whose whole path, laser spot -> scene -> sensed point, is 2 j c deltaT (for a confocal
+capture that is the distance j c deltaT from the wall point).  The voxel operators (nlosgr.backproject,
+nlosgr.forward_project) read the field; the Gaussian renderer is confocal only, and volume_geometry refuses it.
 """
 import numpy as np
 import torch
@@ -61,17 +68,39 @@ def load_irf(path):
     return IRF(taps, center, background)
 
 
+def load_lasers(path):
+    """The laser spots of a non-confocal capture, float32 [3, H*W] or [3, 1], from the optional field
+    `laserGridPositions`, or None when the file has none (a confocal capture)."""
+    import scipy.io
+    m = scipy.io.loadmat(path, variable_names=("laserGridPositions", "cameraGridPositions"))
+    if "laserGridPositions" not in m:
+        return None
+    lasers = np.asarray(m["laserGridPositions"], dtype=np.float32)
+    n = np.asarray(m["cameraGridPositions"]).size // 3 if "cameraGridPositions" in m else None
+    # anything but [3, n] / [3, 1] is refused, an [n, 3] array included: reshaping it would scramble the spots
+    if lasers.ndim != 2 or lasers.shape[0] != 3 or (lasers.shape[1] != 1 and n is not None and lasers.shape[1] != n):
+        raise ValueError(f"nlosgr: {path}: laserGridPositions must be [3, {n if n is not None else 'H*W'}] or [3, 1], "
+                         f"got {list(lasers.shape)}")
+    return lasers
+
+
 def save_zaragoza(path, nlos_data, camera_grid_positions, volume_position, volume_size, deltaT, c,
-                  camera_position=(0.0, 0.0, 0.0), camera_grid_size=None, camera_grid_points=None, irf=None):
+                  camera_position=(0.0, 0.0, 0.0), camera_grid_size=None, camera_grid_points=None, irf=None,
+                  laser_grid_positions=None):
     """Write a capture (or a rendered volume) in the same format load_zaragoza reads; irf (nlosgr.irf.IRF)
-    adds the optional fields load_irf reads."""
+    adds the optional fields load_irf reads, laser_grid_positions ([3, H*W] or [3, 1]) the one load_lasers reads."""
     import scipy.io
     T, H, W = nlos_data.shape
     extra = {}
+    if laser_grid_positions is not None:
+        lasers = np.asarray(laser_grid_positions, dtype=np.float32)
+        if lasers.ndim != 2 or lasers.shape[0] != 3 or lasers.shape[1] not in (1, H * W):
+            raise ValueError(f"nlosgr: laser_grid_positions must be [3, {H * W}] or [3, 1]")
+        extra["laserGridPositions"] = lasers
     if irf is not None:
-        extra = {"irf": irf.taps.detach().cpu().numpy().astype(np.float32).reshape(1, -1),
-                 "irfCenter": np.asarray([[irf.center]], dtype=np.int32),
-                 "background": np.asarray([[irf.background]], dtype=np.float64)}
+        extra.update({"irf": irf.taps.detach().cpu().numpy().astype(np.float32).reshape(1, -1),
+                      "irfCenter": np.asarray([[irf.center]], dtype=np.int32),
+                      "background": np.asarray([[irf.background]], dtype=np.float64)})
     scipy.io.savemat(path, {
         **extra,
         "data": np.asarray(nlos_data, dtype=np.float32),
@@ -126,12 +155,32 @@ def make_data_kwargs(path, device, shuffle=True):
     irf = load_irf(path)
     if irf is not None:   # the capture's temporal response: compute_loss and TrainStep(irf=...) apply it
         data_kwargs["irf"] = irf.to(device)
+    lasers = load_lasers(path)
+    if lasers is not None:   # a non-confocal capture: one laser spot per column of camera_grid_positions, or one
+        lasers = torch.from_numpy(lasers).to(device)
+        if shuffle and lasers.shape[1] > 1:
+            lasers = lasers[:, index.long()]          # column v is the laser of original measurement index[v]
+        data_kwargs["laser_grid_positions"] = lasers
     return data_kwargs, nlos_data, grid_pos_t, index
+
+
+def is_confocal(data_kwargs):
+    """False when data_kwargs holds laser spots that differ from the sensed points."""
+    lasers = data_kwargs.get("laser_grid_positions")
+    if lasers is None:
+        return True
+    sensors = data_kwargs["camera_grid_positions"]
+    return bool(torch.equal(lasers.float().expand_as(sensors), sensors.float().to(lasers.device)))
 
 
 def volume_geometry(data_kwargs, ns, start, end, preset="cuda", mode="noocl"):
     """Batched sampling tables for every wall point of data_kwargs, in the (shuffled) column order of
-    nlos_data.reshape(L, M*N): wall point v = m*N + n is column v (nlos_helpers.py:302-306)."""
+    nlos_data.reshape(L, M*N): wall point v = m*N + n is column v (nlos_helpers.py:302-306).  A non-confocal
+    capture raises NotImplementedError: the tables are spherical shells around each wall point."""
+    if not is_confocal(data_kwargs):
+        raise NotImplementedError("nlosgr: the Gaussian renderer is confocal only: this capture's laser spots "
+                                  "(laser_grid_positions) differ from its sensed points.  Use nlosgr.backproject / "
+                                  "nlosgr.forward_project, which take lasers=")
     walls = data_kwargs["camera_grid_positions"].t().contiguous().float()
     vp = data_kwargs["volume_position"]
     return build_geometry(walls, data_kwargs["volume_box_point"].float(), ns, start, end, data_kwargs["c"],

@@ -10,6 +10,12 @@ pass (nlosgr_forward_project: a workgroup per wall point and voxel split, 64-bit
 row, no float atomics): bitwise repeatable and independent of the split.  A non-finite voxel makes every row
 NaN.  Negative powers are the physical falloff; they need r0 >= 2 dr.  No CPU fallback, no backward.
 
+A non-confocal capture (`lasers=`: the laser lights another wall point than the one sensed) replaces d by half
+the path, g = (|x - laser_i| + |x - wall_i|) / 2, and d^2 by m = |x - laser_i| |x - wall_i| (weight m^(power/2),
+-4 the physical 1 / (dl^2 ds^2)), through nlosgr_forward_project_nc; a negative power then leaves out the pairs
+closer than `dmin` to the laser or the sensed point.  In either kind of file deltaT is the bin width in HALF-path
+units: bin j of a row holds the light whose whole path is 2 (r0 + j c deltaT).
+
     python -m nlosgr.forward_project CAPTURE.mat --resolution R --start S --end E [--power P] [--iterations N]
         --out lw.npz [--mesh lw.ply --level-frac F]
 """
@@ -20,17 +26,35 @@ import numpy as np
 import torch
 
 from . import _lib
-from .backproject import _gpu_f32, backproject, fp32_window
+from .backproject import _gpu_f32, _lasers_arg, backproject, capture_lasers, fp32_window
 from .voxelize import VoxelGrid, front_view
 
 
 @torch.no_grad()
-def forward_project(volume, walls, grid, r0, dr, nr, power=0, out=None, accumulate=False, nsplit=0):
+def box_distance(points, grid):
+    """The smallest distance from any of points [n, 3] to the bounding box of the grid's voxel centres (0 when a
+    point is inside or on it): a float, one host read."""
+    lo = torch.tensor([float(t[0]) for t in grid.tables], device=points.device)
+    hi = torch.tensor([float(t[-1]) for t in grid.tables], device=points.device)
+    lo, hi = torch.minimum(lo, hi), torch.maximum(lo, hi)
+    p = points.double()
+    gap = torch.clamp(torch.maximum(lo.double() - p, p - hi.double()), min=0.0)
+    return float(gap.square().sum(dim=1).sqrt().min())
+
+
+@torch.no_grad()
+def forward_project(volume, walls, grid, r0, dr, nr, power=0, out=None, accumulate=False, nsplit=0, lasers=None,
+                    dmin=None):
     """[nwall, nr] fp32 (the layout data.volume_target returns): the transients of volume [nx, ny, nz] on `grid`
     (voxelize.VoxelGrid) at walls [nwall, 3].  r0: radius of bin 0; dr: bin width; power -4..4: weight d^power.
     out: an [nwall, nr] tensor to write (accumulate=False) or to add this call's rounded sum to
     (accumulate=True: a volume projected as sub-grids or per rank).  nsplit: voxel splits per wall point, 0 = the
-    library's choice; the result does not depend on it."""
+    library's choice; the result does not depend on it.  lasers: None for a confocal capture; else the laser
+    spots [nwall, 3], or [1, 3] for one spot, of a non-confocal capture whose walls are the sensed points (r0 and
+    dr then count half the path, the weight is (|x - laser| |x - wall|)^(power/2)).  dmin (with lasers and a
+    negative power only): pairs closer than dmin to their laser spot or sensed point are left out; None takes
+    the smallest distance from any of those points to the grid's bounding box (one host read, rounded down to
+    fp32) and raises when that is 0.  dmin without lasers raises."""
     lib = _lib.load()
     volume, walls = _gpu_f32(volume, "forward_project"), _gpu_f32(walls, "forward_project")
     if not isinstance(grid, VoxelGrid):
@@ -58,12 +82,35 @@ def forward_project(volume, walls, grid, r0, dr, nr, power=0, out=None, accumula
     xs, ys, zs = grid.on(dev)
     vg = _lib.VoxelGrid(shape[0], shape[1], shape[2], _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(zs))
     opt = _lib.ForwardProjectOpts(*fp32_window(r0, dr), int(power), int(bool(accumulate)), int(nsplit))
-    nbytes = lib.nlosgr_forward_project_workspace_bytes(nwall, nr, ctypes.byref(vg), ctypes.byref(opt))
+    if lasers is None:
+        if dmin is not None:
+            raise ValueError("nlosgr: dmin= belongs to a non-confocal call (lasers=); a confocal one has no use for it")
+        nbytes = lib.nlosgr_forward_project_workspace_bytes(nwall, nr, ctypes.byref(vg), ctypes.byref(opt))
+    else:
+        lasers = _lasers_arg(lasers, walls, "forward_project")
+        if int(power) >= 0:
+            dmin = 0.0                                   # (ignored by the library)
+        elif dmin is None:
+            # rounded DOWN to fp32 (the library takes a float): no pair at that very distance is left out
+            dmin = box_distance(torch.cat([walls, lasers]), grid) if nwall else 1.0
+            f = np.float32(dmin)
+            dmin = float(f if float(f) <= dmin else np.nextafter(f, np.float32(0.0)))
+            if not dmin > 0:
+                raise ValueError("nlosgr: a sensor or laser point lies inside the grid's bounding box, so a negative "
+                                 "power has no bound on its weight: pass dmin= (pairs closer than dmin are left out)")
+        nl = int(lasers.shape[0])
+        nbytes = lib.nlosgr_forward_project_nc_workspace_bytes(nl, nwall, nr, ctypes.byref(vg), ctypes.byref(opt),
+                                                               float(dmin))
     if nbytes == 0:
         raise RuntimeError("nlosgr error: " + lib.nlosgr_last_error().decode(errors="replace"))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    _lib.check(lib.nlosgr_forward_project(_lib.ptr(volume), _lib.ptr(walls), nwall, nr, ctypes.byref(vg),
-                                          ctypes.byref(opt), _lib.ptr(ws), _lib.ptr(out), _lib.stream_handle(dev)))
+    if lasers is None:
+        _lib.check(lib.nlosgr_forward_project(_lib.ptr(volume), _lib.ptr(walls), nwall, nr, ctypes.byref(vg),
+                                              ctypes.byref(opt), _lib.ptr(ws), _lib.ptr(out), _lib.stream_handle(dev)))
+    else:
+        _lib.check(lib.nlosgr_forward_project_nc(_lib.ptr(volume), _lib.ptr(walls), _lib.ptr(lasers), nl, nwall, nr,
+                                                 ctypes.byref(vg), ctypes.byref(opt), float(dmin), _lib.ptr(ws),
+                                                 _lib.ptr(out), _lib.stream_handle(dev)))
     return out
 
 
@@ -96,9 +143,10 @@ def voxel_transient(volume, grid, walls, r, c_deltaT, y):
 
 
 @torch.no_grad()
-def operator_norm(walls, grid, r0, dr, nr, power=0, iterations=8):
+def operator_norm(walls, grid, r0, dr, nr, power=0, iterations=8, lasers=None):
     """The largest eigenvalue of A^T A (A = forward_project with this window and power 0..4) by power iteration
-    from the all-ones volume: a float, one host read at the end.  1 / operator_norm is the Landweber step."""
+    from the all-ones volume: a float, one host read at the end.  1 / operator_norm is the Landweber step.
+    lasers: as forward_project."""
     walls = _gpu_f32(walls, "operator_norm")
     if not isinstance(grid, VoxelGrid):
         raise TypeError("nlosgr: grid must be a voxelize.VoxelGrid")
@@ -108,18 +156,20 @@ def operator_norm(walls, grid, r0, dr, nr, power=0, iterations=8):
     lam = None
     for _ in range(int(iterations)):
         v = v / v.double().norm().float()
-        w = backproject(forward_project(v, walls, grid, r0, dr, nr, power=power), walls, grid, r0, dr, power=power)
+        w = backproject(forward_project(v, walls, grid, r0, dr, nr, power=power, lasers=lasers), walls, grid, r0, dr,
+                        power=power, lasers=lasers)
         lam = w.double().norm()
         v = w
     return float(lam)
 
 
 @torch.no_grad()
-def landweber(rows, walls, grid, r0, dr, power=0, iterations=30, nonneg=True, step=None, x0=None):
+def landweber(rows, walls, grid, r0, dr, power=0, iterations=30, nonneg=True, step=None, x0=None, lasers=None):
     """(volume [nx, ny, nz], objective [iterations]): projected gradient on 1/2 |A v - h|^2,
     v <- max(v - step A^T (A v - h), 0) from x0 (zeros by default), step = 1 / operator_norm by default, power
     0..4 (the range of A^T; for the falloff scale the rows by r^q first, as the back-projection's users do).
-    objective[n] is 1/2 |A v - h|^2 BEFORE update n, a device tensor (no host read inside the loop)."""
+    objective[n] is 1/2 |A v - h|^2 BEFORE update n, a device tensor (no host read inside the loop).
+    lasers: as forward_project (a non-confocal capture)."""
     rows, walls = _gpu_f32(rows, "landweber"), _gpu_f32(walls, "landweber")
     if rows.dim() != 2 or walls.dim() != 2 or walls.shape[1] != 3 or walls.shape[0] != rows.shape[0]:
         raise ValueError("nlosgr: landweber takes rows [nwall, nr] and walls [nwall, 3]")
@@ -129,7 +179,7 @@ def landweber(rows, walls, grid, r0, dr, power=0, iterations=30, nonneg=True, st
         raise ValueError("nlosgr: landweber takes a power in 0..4 (the range of backproject)")
     nr = int(rows.shape[1])
     if step is None:
-        step = 1.0 / operator_norm(walls, grid, r0, dr, nr, power=power)
+        step = 1.0 / operator_norm(walls, grid, r0, dr, nr, power=power, lasers=lasers)
     step = float(step)
     if x0 is None:
         v = torch.zeros(grid.shape, device=rows.device)
@@ -140,10 +190,10 @@ def landweber(rows, walls, grid, r0, dr, power=0, iterations=30, nonneg=True, st
     objective = torch.zeros(int(iterations), dtype=torch.float64, device=rows.device)
     res = torch.empty_like(rows)
     for n in range(int(iterations)):
-        forward_project(v, walls, grid, r0, dr, nr, power=power, out=res)
+        forward_project(v, walls, grid, r0, dr, nr, power=power, out=res, lasers=lasers)
         res.sub_(rows)
         objective[n] = 0.5 * res.double().square().sum()
-        v.sub_(backproject(res, walls, grid, r0, dr, power=power), alpha=step)
+        v.sub_(backproject(res, walls, grid, r0, dr, power=power, lasers=lasers), alpha=step)
         if nonneg:
             v.clamp_(min=0.0)
     return v, objective
@@ -152,7 +202,8 @@ def landweber(rows, walls, grid, r0, dr, power=0, iterations=30, nonneg=True, st
 @torch.no_grad()
 def landweber_capture(data_kwargs, resolution, start, end, power=0, iterations=30):
     """Landweber on the capture in data_kwargs (data.make_data_kwargs) over bins [floor(start), floor(start) +
-    end - start) onto VoxelGrid(volume_position, volume_size, resolution), as backproject_capture lays it out.
+    end - start) onto VoxelGrid(volume_position, volume_size, resolution), as backproject_capture lays it out; a
+    non-confocal capture (data_kwargs["laser_grid_positions"]) with its laser spots.
     Returns {"volume", "objective", "front", "depth", "grid"}."""
     from .data import volume_target
     I1 = int(np.floor(start))
@@ -161,15 +212,17 @@ def landweber_capture(data_kwargs, resolution, start, end, power=0, iterations=3
     vp = data_kwargs["volume_position"]
     grid = VoxelGrid([float(v) for v in vp], float(data_kwargs["volume_size"]), resolution)
     cdt = float(data_kwargs["c"]) * float(data_kwargs["deltaT"])
-    vol, obj = landweber(rows, walls, grid, I1 * cdt, cdt, power=power, iterations=iterations)
+    vol, obj = landweber(rows, walls, grid, I1 * cdt, cdt, power=power, iterations=iterations,
+                         lasers=capture_lasers(data_kwargs))
     front, depth = front_view(vol, grid)
     return {"volume": vol, "objective": obj, "front": front, "depth": depth, "grid": grid}
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m nlosgr.forward_project",
-                                 description="Least-squares voxel volume of a confocal capture (Landweber iteration "
-                                             "with the forward projector and the back-projection).")
+                                 description="Least-squares voxel volume of a confocal or non-confocal capture (the "
+                                             "optional field laserGridPositions): Landweber iteration with the "
+                                             "forward projector and the back-projection.")
     ap.add_argument("capture", help="Zaragoza-format .mat file")
     ap.add_argument("--resolution", type=int, default=64)
     ap.add_argument("--start", type=int, required=True, help="first time bin")

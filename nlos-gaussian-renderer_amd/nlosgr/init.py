@@ -10,7 +10,9 @@ image lacks: it raises.
 
 `sample_from_backprojection` is an addition without a counterpart in the reference: it draws the initial
 points from the capture's back-projection (nlosgr.backproject) instead of a carved set, so it does not depend
-on a first-bounce threshold and works on captures with a dark-count floor and shot noise.
+on a first-bounce threshold and works on captures with a dark-count floor and shot noise.  It also takes a
+non-confocal capture (data_kwargs["laser_grid_positions"]: the laser spot differs from the sensed one), which
+the carving cannot; in such a file deltaT is the bin width in half-path units, as in a confocal one.
 """
 import numpy as np
 import torch
