@@ -439,6 +439,36 @@ NLOSGR_API int nlosgr_voxelize(const nlosgr_gaussians* g, const nlosgr_voxel_gri
                     const nlosgr_options* opt, void* workspace, float* density_out, float* albedo_out,
                     void* hip_stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Backward of nlosgr_voxelize (ABI 13, an addition): with L a function of the two volumes and
+ * grad_density = dL/d density, grad_albedo = dL/d albedo_density [nx,ny,nz] (either may be NULL: that volume
+ * does not enter L), the gradients of L with respect to the raw parameters of `g`, in the layout of
+ * nlosgr_render_bwd: d_mu [ng,3], d_scaling [ng,3], d_rotation [ng,4], d_opacity [ng], d_features [ng,k_feat]
+ * with zero in columns >= (sh_degree+1)^2.  The albedo's clamp passes gradient where 0.5 + SH >= 0.
+ *   support      a (voxel, Gaussian) pair contributes iff it contributes to nlosgr_voxelize under the same
+ *                arguments (the same cutoff box and the same fp32 mask), and a pair outside is dropped, not
+ *                multiplied by zero: a non-finite upstream value reaches exactly the Gaussians whose support
+ *                holds that voxel.  cutoff <= 0 is dense (every pair; slow, for tests).  In culled mode a
+ *                Gaussian whose cutoff box is empty or not finite gets all-zero rows, as the forward skips it.
+ *   determinism  a Gaussian's rows depend on that Gaussian, the grid tables, cam, opt->cutoff and the upstream
+ *                alone, not on ng, the other Gaussians or the launch shape; no atomics.  Two runs are bitwise
+ *                equal, and permuting the Gaussians permutes the rows bitwise.
+ *   outputs      overwritten.  Both upstream pointers NULL: the five outputs are zero-filled.  ng == 0: nothing
+ *                is written, nothing is launched.
+ *   validation   on the host before any launch: nlosgr_voxelize's, plus NLOSGR_E_INVALID for a NULL cam and,
+ *                when ng > 0, a NULL output or workspace.
+ * The library neither allocates nor synchronises.
+ * ------------------------------------------------------------------------------------- */
+
+/* Scratch bytes for nlosgr_voxelize_bwd (host only; 0 with a message in nlosgr_last_error on invalid input). */
+NLOSGR_API size_t nlosgr_voxel_bwd_workspace_bytes(const nlosgr_gaussians* g, const nlosgr_voxel_grid* grid,
+                                        const nlosgr_options* opt);
+
+NLOSGR_API int nlosgr_voxelize_bwd(const nlosgr_gaussians* g, const nlosgr_voxel_grid* grid, const float* cam,
+                        const nlosgr_options* opt, void* workspace, const float* grad_density,
+                        const float* grad_albedo, float* d_mu, float* d_scaling, float* d_rotation,
+                        float* d_opacity, float* d_features, void* hip_stream);
+
 /* Maximum of vol [nx,ny,nz] along `axis` (0..2) and the index of that maximum (ties: lowest index, so an
  * all-zero column gives (0, 0)); max_out (float) / argmax_out (int32), either may be NULL, are laid out as
  * the two remaining axes in their original order. */

@@ -272,6 +272,36 @@ __device__ void chain_to_raw_shape(const nlosgr_gaussians& g, int i, const float
     chain_core<PRESET>(g, i, a, dRp, dst, d_scaling, d_rot);
 }
 
+// The part of a per-Gaussian backward finish that does not depend on where the sums came from (rays finish,
+// voxelizer backward): dmu[3] = the direct dL/dmu, dsig = dL/dsigma, drho = dL/drho of Gaussian i, with
+// rho = max(0, 0.5 + SH(dir(mu - cam))) and sh the caller's value of SH (clamp_min passes the gradient where
+// 0.5 + sh >= 0).  Writes d_mu (the direct term plus the albedo's through the view direction), d_opac
+// (through the sigmoid) and d_feat [k_feat] (zero in columns >= (deg+1)^2).  MAXK: the caller's SH capacity.
+template <int PRESET, int MAXK>
+__device__ __forceinline__ void albedo_chain(const nlosgr_gaussians& g, int i, const float* cam, float sh,
+                                             float* dmu, float dsig, float drho, float* d_mu, float* d_opac,
+                                             float* d_feat) {
+    const float mx = g.mu[3 * i], my = g.mu[3 * i + 1], mz = g.mu[3 * i + 2];
+    float dx, dy, dz, nrm;
+    view_dir<PRESET>(mx - cam[0], my - cam[1], mz - cam[2], dx, dy, dz, nrm);
+    const float gr = sh + 0.5f >= 0.f ? drho : 0.f;
+    float Y[MAXK];
+    sh_basis<PRESET>(g.sh_degree, dx, dy, dz, Y);
+    const int K = (g.sh_degree + 1) * (g.sh_degree + 1);
+    const int kf = g.k_feat;
+    for (int c = 0; c < kf; ++c) d_feat[(size_t)i * kf + c] = c < K ? gr * Y[c] : 0.f;
+    if (gr != 0.f) {
+        float gx, gy, gz;
+        sh_grad_dir<PRESET>(g.sh_degree, dx, dy, dz, g.features + (size_t)i * kf, gx, gy, gz);
+        float ox, oy, oz;
+        view_dir_bwd<PRESET>(mx - cam[0], my - cam[1], mz - cam[2], nrm, gr * gx, gr * gy, gr * gz, ox, oy, oz);
+        dmu[0] += ox; dmu[1] += oy; dmu[2] += oz;
+    }
+    d_mu[3 * i] = dmu[0]; d_mu[3 * i + 1] = dmu[1]; d_mu[3 * i + 2] = dmu[2];
+    const float sg = 1.0f / (1.0f + expf(-g.opacity[i]));
+    d_opac[i] = dsig * sg * (1.0f - sg);
+}
+
 // ray-tile engine (nlosgr_tiles.hip): NLOSGR_MODE_OCCL and NLOSGR_SELECT_AABB
 bool tiles_engine(const nlosgr_options* opt);
 int tiles_validate(const nlosgr_gaussians* g, const nlosgr_geometry* geo, const nlosgr_options* opt);

@@ -335,29 +335,9 @@ __global__ __launch_bounds__(kBlock) void rays_finish_kernel(RArgs k, float* d_m
         for (int t = 0; t < 16; ++t) acc[t] += k.acc[((size_t)s * k.g.ng + i) * 16 + t];
     const float mx = k.g.mu[3 * i], my = k.g.mu[3 * i + 1], mz = k.g.mu[3 * i + 2];
     float dmu[3] = {acc[9], acc[10], acc[11]};
-    const float drho = acc[13];
-    // rho = max(0, 0.5 + SH(dir(mu - cam))); clamp_min passes the gradient where 0.5 + SH >= 0
-    float dx, dy, dz, nrm;
-    view_dir<PRESET>(mx - k.r.cam[0], my - k.r.cam[1], mz - k.r.cam[2], dx, dy, dz, nrm);
     float sh;
     albedo<PRESET>(k.g, i, mx, my, mz, k.r.cam, sh);
-    const float gr = sh + 0.5f >= 0.f ? drho : 0.f;
-    float Y[kMaxK];
-    sh_basis<PRESET>(k.g.sh_degree, dx, dy, dz, Y);
-    const int K = (k.g.sh_degree + 1) * (k.g.sh_degree + 1);
-    const int kf = k.g.k_feat;
-    for (int c = 0; c < kf; ++c) d_feat[(size_t)i * kf + c] = c < K ? gr * Y[c] : 0.f;
-    if (gr != 0.f) {
-        float gx, gy, gz;
-        sh_grad_dir<PRESET>(k.g.sh_degree, dx, dy, dz, k.g.features + (size_t)i * kf, gx, gy, gz);
-        float ox, oy, oz;
-        view_dir_bwd<PRESET>(mx - k.r.cam[0], my - k.r.cam[1], mz - k.r.cam[2], nrm, gr * gx, gr * gy, gr * gz, ox,
-                             oy, oz);
-        dmu[0] += ox; dmu[1] += oy; dmu[2] += oz;
-    }
-    d_mu[3 * i] = dmu[0]; d_mu[3 * i + 1] = dmu[1]; d_mu[3 * i + 2] = dmu[2];
-    const float sg = 1.0f / (1.0f + expf(-k.g.opacity[i]));
-    d_opac[i] = acc[12] * sg * (1.0f - sg);
+    albedo_chain<PRESET, kMaxK>(k.g, i, k.r.cam, sh, dmu, acc[12], acc[13], d_mu, d_opac, d_feat);
     chain_to_raw<PRESET>(k.g, i, acc, d_scaling, d_rot);
 }
 

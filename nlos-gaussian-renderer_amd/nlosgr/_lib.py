@@ -109,7 +109,8 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_rays_bwd", "nlosgr_rays_analytic", "nlosgr_mse_workspace_bytes", "nlosgr_mse", "nlosgr_adam",
            "nlosgr_irf_apply", "nlosgr_mse_irf_workspace_bytes", "nlosgr_mse_irf",
            "nlosgr_loss_irf_workspace_bytes", "nlosgr_loss_irf",
-           "nlosgr_carve_votes", "nlosgr_voxel_workspace_bytes", "nlosgr_voxelize", "nlosgr_volume_project",
+           "nlosgr_carve_votes", "nlosgr_voxel_workspace_bytes", "nlosgr_voxelize", "nlosgr_voxel_bwd_workspace_bytes",
+           "nlosgr_voxelize_bwd", "nlosgr_volume_project",
            "nlosgr_mesh_workspace_bytes", "nlosgr_mesh_count", "nlosgr_mesh_emit", "nlosgr_backproject",
            "nlosgr_forward_project_workspace_bytes", "nlosgr_forward_project",
            "nlosgr_backproject_nc", "nlosgr_forward_project_nc_workspace_bytes", "nlosgr_forward_project_nc",
@@ -178,6 +179,10 @@ def load():
     lib.nlosgr_voxel_workspace_bytes.restype = ctypes.c_size_t
     lib.nlosgr_voxelize.argtypes = [PG, PVG, _P, POPT, _P, _P, _P, _P]
     lib.nlosgr_voxelize.restype = ctypes.c_int
+    lib.nlosgr_voxel_bwd_workspace_bytes.argtypes = [PG, PVG, POPT]
+    lib.nlosgr_voxel_bwd_workspace_bytes.restype = ctypes.c_size_t
+    lib.nlosgr_voxelize_bwd.argtypes = [PG, PVG, _P, POPT, _P, _P, _P, _P, _P, _P, _P, _P, _P]
+    lib.nlosgr_voxelize_bwd.restype = ctypes.c_int
     lib.nlosgr_volume_project.argtypes = [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]
     lib.nlosgr_volume_project.restype = ctypes.c_int
     lib.nlosgr_mesh_workspace_bytes.argtypes = [PVG]

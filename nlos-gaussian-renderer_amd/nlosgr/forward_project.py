@@ -8,7 +8,7 @@ volume (Landweber iteration).  For voxel centre x and wall point i (include/nlos
 with d, u, k, f the fp32 values nlosgr_backproject forms, so <A v, h> = <v, A^T h> for powers 0..4.  One HIP
 pass (nlosgr_forward_project: a workgroup per wall point and voxel split, 64-bit fixed-point adds into an LDS
 row, no float atomics): bitwise repeatable and independent of the split.  A non-finite voxel makes every row
-NaN.  Negative powers are the physical falloff; they need r0 >= 2 dr.  No CPU fallback, no backward.
+NaN.  Negative powers are the physical falloff; they need r0 >= 2 dr.  No CPU fallback; `project` is the autograd front (its backward is backproject).
 
 A non-confocal capture (`lasers=`: the laser lights another wall point than the one sensed) replaces d by half
 the path, g = (|x - laser_i| + |x - wall_i|) / 2, and d^2 by m = |x - laser_i| |x - wall_i| (weight m^(power/2),
@@ -112,6 +112,30 @@ def forward_project(volume, walls, grid, r0, dr, nr, power=0, out=None, accumula
                                                  ctypes.byref(vg), ctypes.byref(opt), float(dmin), _lib.ptr(ws),
                                                  _lib.ptr(out), _lib.stream_handle(dev)))
     return out
+
+
+class _ProjectFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, volume, walls, grid, r0, dr, nr, power, lasers):
+        ctx.conf = (walls, grid, r0, dr, power, lasers)
+        return forward_project(volume, walls, grid, r0, dr, nr, power=power, lasers=lasers)
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        walls, grid, r0, dr, power, lasers = ctx.conf
+        return (backproject(grad_rows, walls, grid, r0, dr, power=power, lasers=lasers),) + (None,) * 7
+
+
+def project(volume, walls, grid, r0, dr, nr, power=0, lasers=None):
+    """forward_project as a differentiable function of the volume: the forward is forward_project(volume, walls,
+    grid, r0, dr, nr, power=, lasers=), the backward with respect to `volume` is backproject of the upstream rows
+    with the same arguments (the pair is an exact adjoint).  A volume that requires grad takes powers 0..4 only:
+    back-projection has no negative power, so a negative one would have no backward; for the physical falloff
+    scale the rows first, as landweber documents."""
+    if isinstance(volume, torch.Tensor) and volume.requires_grad and not 0 <= int(power) <= 4:
+        raise ValueError("nlosgr: project differentiates through backproject, which takes powers 0..4 only; a volume "
+                         f"that requires grad cannot take power {int(power)} (scale the rows by r^q instead)")
+    return _ProjectFn.apply(volume, walls, grid, r0, dr, int(nr), int(power), lasers)
 
 
 def _spacing(t):

@@ -13,7 +13,11 @@ with preset, scaling_modifier, sh_degree and cutoff meaning exactly what they me
 (pdf_g = 0 where the Mahalanobis distance exceeds `cutoff`; dense when cutoff <= 0).  One HIP pass
 (nlosgr_voxelize: two-level box culling, ordered LDS batches) replaces the dense [Ng, Nvox] torch
 broadcast; every voxel's sum runs in ascending Gaussian order, so the result is bitwise repeatable and a
-sub-grid (VoxelGrid.slice) gives exactly the numbers of the full grid.  No CPU fallback, no backward.
+sub-grid (VoxelGrid.slice) gives exactly the numbers of the full grid.  No CPU fallback.
+
+The backward is nlosgr_voxelize_bwd (voxelize_backward; voxelize_params is the torch.autograd front of the
+pair): one wave per Gaussian sums the upstream over the Gaussian's own support, the forward's by construction,
+without atomics, so a Gaussian's gradient rows do not depend on the other Gaussians or their order.
 
     python -m nlosgr.voxelize CKPT --resolution 256 --cutoff 3 --volume-position x y z --volume-size s --out recon.npz
 """
@@ -122,6 +126,90 @@ def voxelize(model, grid, cam, preset="cuda", cutoff=3.0, scaling_modifier=1.0, 
     _lib.check(lib.nlosgr_voxelize(g, vg, _lib.ptr(cam), opt, _lib.ptr(ws), _lib.ptr(dens), _lib.ptr(alb),
                                    _lib.stream_handle(dev)))
     return dens, alb
+
+
+@torch.no_grad()
+def voxelize_backward(model, grid, cam, grad_density=None, grad_albedo=None, preset="cuda", cutoff=3.0,
+                      scaling_modifier=1.0, sh_degree=None):
+    """(d_mu [ng,3], d_scaling [ng,3], d_rotation [ng,4], d_opacity [ng], d_features [ng,K]), the tuple layout of
+    render_backward: the gradients of L with respect to the raw parameters of `model`, given grad_density =
+    dL/d density and grad_albedo = dL/d albedo_density, each [nx, ny, nz] or None, for the volumes voxelize
+    returns under the same arguments.  One nlosgr_voxelize_bwd launch sequence on the current stream; both
+    upstreams None gives zeros."""
+    lib = _lib.load()
+    mu, scaling, rotation, opacity, feats = [_gpu_f32(t, "voxelize_backward") for t in
+                                             (model._mu, model._scaling, model._rotation, model._opacity,
+                                              features_flat(model))]
+    cam = _gpu_f32(cam, "voxelize_backward").reshape(-1)
+    if cam.numel() != 3:
+        raise ValueError("nlosgr: cam must have 3 elements")
+    dev = mu.device
+    ng = mu.shape[0]
+    if mu.shape != (ng, 3) or scaling.shape != (ng, 3) or rotation.shape != (ng, 4) or opacity.numel() != ng:
+        raise ValueError("nlosgr: mu/scaling must be [Ng,3], rotation [Ng,4], opacity [Ng]")
+    nx, ny, nz = grid.shape
+    ups = []
+    for t in (grad_density, grad_albedo):
+        if t is not None:
+            t = _gpu_f32(t, "voxelize_backward")
+            if tuple(t.shape) != (nx, ny, nz) or t.device != dev:
+                raise ValueError(f"nlosgr: an upstream gradient must be a {(nx, ny, nz)} tensor on {dev}")
+        ups.append(t)
+    deg = int(model.active_sh_degree if sh_degree is None else sh_degree)
+    g = _lib.Gaussians(ng, feats.shape[1], deg, _lib.PRESETS[preset], float(scaling_modifier), _lib.ptr(mu),
+                       _lib.ptr(scaling), _lib.ptr(rotation), _lib.ptr(opacity), _lib.ptr(feats))
+    xs, ys, zs = grid.on(dev)
+    vg = _lib.VoxelGrid(nx, ny, nz, _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(zs))
+    opt = _lib.Options(_lib.MODE_NOOCL, float(cutoff), 0.0, 1.0, 0, 0, 0, _lib.SELECT_SUPPORT, 0, 0)
+    nbytes = lib.nlosgr_voxel_bwd_workspace_bytes(g, vg, opt)
+    if nbytes == 0:
+        _lib.check(1)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    outs = (torch.empty_like(mu), torch.empty_like(scaling), torch.empty_like(rotation),
+            torch.empty(ng, device=dev), torch.empty_like(feats))
+    _lib.check(lib.nlosgr_voxelize_bwd(g, vg, _lib.ptr(cam), opt, _lib.ptr(ws), _lib.ptr(ups[0]), _lib.ptr(ups[1]),
+                                       *[_lib.ptr(o) for o in outs], _lib.stream_handle(dev)))
+    return outs
+
+
+class _Raw:
+    """The five raw tensors under the reference's attribute names (features [ng, K] split as dc | rest)."""
+
+    def __init__(self, mu, scaling, rotation, opacity, features, deg):
+        self._mu, self._scaling, self._rotation, self._opacity = mu, scaling, rotation, opacity
+        self._features_dc, self._features_rest = features[:, :1], features[:, 1:]
+        self.active_sh_degree = int(deg)
+
+
+class _VoxelizeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mu, scaling, rotation, opacity, features, grid, cam, preset, cutoff, mod, deg, want_d, want_a):
+        raw = _Raw(mu, scaling, rotation, opacity, features, deg)
+        dens, alb = voxelize(raw, grid, cam, preset=preset, cutoff=cutoff, scaling_modifier=mod,
+                             want_density=want_d, want_albedo=want_a)
+        ctx.save_for_backward(mu, scaling, rotation, opacity, features, cam)
+        ctx.conf = (grid, preset, cutoff, mod, deg, opacity.shape)
+        ctx.set_materialize_grads(False)
+        return dens, alb
+
+    @staticmethod
+    def backward(ctx, g_dens, g_alb):
+        mu, scaling, rotation, opacity, features, cam = ctx.saved_tensors
+        grid, preset, cutoff, mod, deg, oshape = ctx.conf
+        raw = _Raw(mu, scaling, rotation, opacity, features, deg)
+        d_mu, d_s, d_q, d_o, d_f = voxelize_backward(raw, grid, cam, g_dens, g_alb, preset=preset, cutoff=cutoff,
+                                                     scaling_modifier=mod)
+        return (d_mu, d_s, d_q, d_o.reshape(oshape), d_f) + (None,) * 8
+
+
+def voxelize_params(mu, scaling, rotation, opacity, features, grid, cam, preset="cuda", cutoff=3.0,
+                    scaling_modifier=1.0, sh_degree=0, want_density=True, want_albedo=True):
+    """voxelize as a differentiable function of the raw parameter tensors (features [ng, K], as
+    model.features_flat lays them out): (density, albedo_density), None where not wanted, the forward exactly
+    voxelize's, the backward voxelize_backward.  An output that is not wanted, or that the loss does not
+    reach, costs nothing in either direction."""
+    return _VoxelizeFn.apply(mu, scaling, rotation, opacity, features, grid, cam, preset, float(cutoff),
+                             float(scaling_modifier), int(sh_degree), bool(want_density), bool(want_albedo))
 
 
 @torch.no_grad()
