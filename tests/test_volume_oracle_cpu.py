@@ -15,6 +15,11 @@ allowance, so the tolerance is not below fp32 noise; (b) four synthetic faults o
 in the float64 reference, are rejected even at the coarsest fixed-point unit the scene allows, while the row-maximum
 figure the earlier forward tests use lets the first two pass; (c) in at least three quarters of the non-empty bins
 neither the dense-culled bracket nor the rounding bound is what decides.
+
+The per-ray outputs, the per-ray upstream, occlusion compositing and AABB selection of the reference are pinned to
+the fp32 oracle (oracle.torch_ref.render_rays_cuda / aabb_filter) and to autograd of single samples; and every scene
+that tests/test_gpu_ray_upstream.py and tests/test_gpu_tile_edges.py judge against the reference is shown to stay 1e-3
+away from the model's discontinuous decisions (volume_oracle.decision_margins): that is where their seeds are proven.
 """
 import pytest
 import torch
@@ -287,3 +292,151 @@ def test_quantile_rule_of_the_bright_scene():
     print("\n(E, E of the largest bound) per number of bright Gaussians:", E)
     assert E[1][0] == E[0][0] and E[1][1] <= E[1][0] - 6
     assert all(E[nb][0] == E[nb][1] == E[1][1] for nb in (2, 3, 30))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# per-ray outputs, the per-ray upstream, occlusion and AABB selection
+# ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode,selection,cutoff,opaque", [
+    ("occl", "support", 0.0, True), ("occl", "support", 0.0, False), ("occl", "support", 5.7, True),
+    ("occl", "aabb", 0.0, False), ("occl", "aabb", 5.7, False), ("noocl", "aabb", 0.0, False), ("noocl", "aabb", 5.7, False)])
+def test_occl_and_aabb_forward_match_fp32_oracle(mode, selection, cutoff, opaque):
+    """The float64 occl / aabb forward against fp32 render_rays_cuda and aabb_filter (pinned to the reference's golden
+    files by test_oracle_golden.py) on a 24-Gaussian scene of 9 x 5 rays and 40 bins, with the T < 1e-4 cut reached
+    (opaque: dead samples exist, and are zero in both) and not: every (ray, bin) within 1e-5 of the tensor's maximum,
+    the rounding of an fp32 sum of 24 terms and of exp (measured: 4e-7); the per-ray lists are identical."""
+    model, geo, cdt = VO.ladder_scene(40, mode=mode, selection=selection)
+    if not opaque:
+        with torch.no_grad():
+            model._opacity.sub_(3.0)
+    bb = VO.boxes_of(model) if selection == "aabb" else None
+    P = VO.params_of_model(model)
+    rs = cdt if mode == "noocl" else 1.0
+    hist, rays, T, sels = VO.forward_rays(P, geo, "cuda", mode, cdt, cutoff, selection, bb, ray_scale=rs)
+    _, ref32, _, lists = VO.fp32_oracle(model, geo, mode, cdt, cutoff, selection, bb, ray_scale=rs)
+    if mode == "occl":
+        assert bool((T < 1e-4).any()) == opaque
+        dead = T.transpose(1, 2) < 1e-4
+        assert float(rays[dead].abs().sum()) == 0.0 and float(ref32[dead].abs().sum()) == 0.0
+        assert bool((ref32[~dead] > 0).any())
+    if selection == "aabb":
+        for p, filt in enumerate(lists):
+            mask = torch.zeros_like(sels[p])
+            for ray in range(filt.shape[0]):
+                mask[filt[ray, 1:1 + int(filt[ray, 0])].long(), ray] = True
+            assert torch.equal(mask, sels[p])
+        assert 0.0 < float(torch.stack(sels).double().mean()) < 1.0
+    err = float((rays - ref32.double()).abs().max() / rays.abs().max())
+    print(f"\n{mode} {selection} cutoff={cutoff} opaque={opaque}: fp32 oracle rays {err:.2e} of the maximum")
+    assert err <= 1e-5
+
+
+def test_aabb_cap_keeps_the_first_256_by_index():
+    """300 boxes that cover every ray: each ray keeps Gaussians 0..255."""
+    model, geo, cdt = VO.window_scene(300, mode="occl", scale_shift=2.5)
+    sel = VO.selection_mask(VO.tables(geo), 0, VO.boxes_of(model))
+    assert bool(sel[:256].all()) and not bool(sel[256:].any())
+
+
+@pytest.mark.parametrize("mode,selection", [("noocl", "support"), ("netf", "support"), ("occl", "support"),
+                                            ("occl", "aabb"), ("noocl", "aabb")])
+def test_rays_sum_to_the_histogram(mode, selection):
+    """hist[p, k] = hscale[p] att[k] sum_rays sin(theta) rays[p, ray, k] / ray_scale."""
+    model, geo, cdt = VO.ladder_scene(65, mode=mode, selection=selection)
+    bb = VO.boxes_of(model) if selection == "aabb" else None
+    ref = VO.reference(VO.params_of_model(model), geo, "cuda", mode, cdt, 5.7, None, None, selection, bb, ray_scale=0.37)
+    tab = VO.tables(geo)
+    st = tab["st"][:, :, None].expand(-1, -1, geo.np).reshape(geo.nwall, -1)
+    h = tab["hscale"][:, None] * tab["att"][None, :] * (ref.rays * st[:, :, None]).sum(dim=1) / 0.37
+    assert float(ref.hist.abs().max()) > 0
+    assert float((h - ref.hist).abs().max()) <= 1e-12 * float(ref.hist.abs().max())
+    assert all(float(g.abs().max()) == 0.0 for g in ref.grads.values())     # no upstream: no gradient
+
+
+@pytest.mark.parametrize("mode,selection,cutoff", [("netf", "support", 5.7), ("occl", "support", 0.0), ("occl", "aabb", 5.7)])
+def test_one_hot_gray_is_the_gradient_of_that_sample(mode, selection, cutoff):
+    """gout = None and a one-hot gray: the gradients equal torch autograd of the single sample rays[p, ray, k]."""
+    model, geo, cdt = VO.ladder_scene(40, mode=mode, selection=selection)
+    bb = VO.boxes_of(model) if selection == "aabb" else None
+    p, ray, k = 1, 3 * geo.np + 2, 17
+    gray = torch.zeros(geo.nwall, geo.nt * geo.np, geo.nr)
+    gray[p, ray, k] = 1.0
+    ref = VO.reference(VO.params_of_model(model), geo, "cuda", mode, cdt, cutoff, None, gray, selection, bb, ray_scale=0.5)
+    P = VO.Params64(VO.params_of_model(model))
+    tab = VO.tables(geo)
+    sel = VO.selection_mask(tab, p, bb) if bb is not None else None
+    out, _ = VO.ray_outputs(P, tab, p, "cuda", mode, cdt, cutoff, sel)
+    sample = 0.5 * out[k, ray]
+    assert float(sample.detach()) > 0 and float(sample.detach()) == float(ref.rays[p, ray, k])
+    want = torch.autograd.grad(sample, P.leaves(), allow_unused=True)
+    for n, w in zip(VO.NAMES, want):
+        w = torch.zeros_like(ref.grads[n]) if w is None else w.reshape(ref.grads[n].shape)
+        assert float((ref.grads[n] - w).abs().max()) <= 1e-12 * max(float(w.abs().max()), 1e-300), n
+        assert bool((ref.scale[n] >= ref.grads[n].abs().amax(dim=1) * (1 - 1e-12)).all())
+
+
+def test_reference_is_linear_in_both_upstreams():
+    """grad(a gout1 + b gout2, a gray1 + b gray2) = a grad(gout1, gray1) + b grad(gout2, gray2); and the hist upstream
+    that a gray reproduces (gray = gout att hscale sin(theta) / ray_scale) gives the same gradient."""
+    model, geo, cdt = VO.ladder_scene(40)
+    Pm = VO.params_of_model(model)
+    g = torch.Generator().manual_seed(3)
+    go = [torch.randn(geo.nwall, geo.nr, generator=g).double() for _ in range(2)]
+    gr = [torch.randn(geo.nwall, geo.nt * geo.np, geo.nr, generator=g).double() for _ in range(2)]
+    f = lambda a, b: VO.reference(Pm, geo, "cuda", "occl", cdt, 5.7, a, b, ray_scale=0.5)
+    r1, r2, r12 = f(go[0], gr[0]), f(go[1], gr[1]), f(2.0 * go[0] - 3.0 * go[1], 2.0 * gr[0] - 3.0 * gr[1])
+    for n in VO.NAMES:
+        want = 2.0 * r1.grads[n] - 3.0 * r2.grads[n]
+        assert float((r12.grads[n] - want).abs().max()) <= 1e-11 * float(r12.scale[n].max()), n
+    eq = VO.equivalent_gray(geo, go[0], 0.5)
+    a, b = f(go[0], None), f(None, eq)
+    for n in VO.NAMES:
+        assert float((a.grads[n] - b.grads[n]).abs().max()) <= 1e-12 * float(a.scale[n].max()), n
+        assert float((a.scale[n] - b.scale[n]).abs().max()) <= 1e-12 * float(a.scale[n].max()), n
+
+
+def _margin_cases():
+    """(name, model, geo, mode, c dT, cutoff, selection): every scene of test_gpu_ray_upstream.py's tile part and of
+    test_gpu_tile_edges.py at every parameter value they use (the pair-major scenes hold no discontinuous decision)."""
+    import test_gpu_ray_upstream as RU
+    import test_gpu_tile_edges as TE
+    for name, (model, geo, cdt), mode, cutoff, selection in list(RU.margin_cases()) + list(TE.margin_cases()):
+        yield name, model, geo, mode, cdt, cutoff, selection
+
+
+def test_decision_margins_of_every_gpu_scene():
+    """Every T_k stays 1e-3 (relative) away from 1e-4 and every slab time 1e-3 of the ray's length away from its
+    decision, in every scene the two GPU files judge against this reference.  A seed that fails is changed in the
+    scene builder; the 1e-3 stays."""
+    worst = {"T": float("inf"), "slab": float("inf")}
+    for name, model, geo, mode, cdt, cutoff, selection in _margin_cases():
+        bb = VO.boxes_of(model) if selection == "aabb" else None
+        m = VO.decision_margins(VO.params_of_model(model), geo, "cuda", mode, cdt, cutoff, selection, bb)
+        print(f"\n{name}: T {m['T']:.2e}, slab {m['slab']:.2e}")
+        assert m["T"] > 1e-3 and m["slab"] > 1e-3, (name, m)
+        worst = {k: min(worst[k], m[k]) for k in worst}
+    print("\nsmallest margins:", worst)
+
+
+def test_opaque_scene_cuts_in_every_chunk():
+    """opaque_scene: by the float64 reference the first dead bin lies in chunk 0 for some rays, in a later chunk for
+    others and nowhere for at least one, at both row lengths."""
+    for nr in (97, 257):
+        model, geo, cdt = VO.opaque_scene(nr)
+        T = VO.forward_rays(VO.params_of_model(model), geo, "cuda", "occl", cdt, 0.0)[2]
+        fd = VO.first_dead_bin(T)
+        assert bool((fd < 64).any()) and bool(((fd >= 64) & (fd < nr)).any()) and bool((fd == nr).any()), fd
+
+
+def test_walk_scene_has_every_class_in_a_sorted_block():
+    """walk_scene: at cutoff 5.0 and 5.7 some block of 64 entries x 4 rays holds more than 64 live pairs (the sorted
+    order) of all four length classes, and walks longer than 200 bins exist."""
+    model, geo, cdt = VO.walk_scene()
+    assert cdt <= 1.0 / 64
+    for cutoff in (5.0, 5.7):
+        L = VO.walk_lengths(model, geo, cutoff)
+        blocks = [b for p in range(geo.nwall) for b in VO.walk_blocks(L, p, 8, 4)]
+        assert any(n > 64 and c == [0, 1, 2, 3] for n, c in blocks)
+        assert int((L > 200).sum()) > 0
+        for lo, hi in ((1, 28), (28, 56), (56, 96), (96, 200)):
+            assert int(((L >= lo) & (L < hi)).sum()) > 0
