@@ -37,7 +37,9 @@
  *   nlosgr_forward_project  no counterpart: the adjoint of the back-projection, voxel grid -> transients
  *                          (checks a volume against the capture; the least-squares volume)
  *   nlosgr_*_nc         no counterpart: the two voxel operators for a non-confocal capture (laser spot and
- *                          sensed spot differ); the Gaussian renderer itself stays confocal
+ *                          sensed spot differ)
+ *   nlosgr_render_nc_*  no counterpart: the Gaussian renderer of such a capture, forward and backward (the
+ *                          no-occlusion histogram; nlosgr_render_fwd / _bwd stay confocal)
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -663,6 +665,67 @@ NLOSGR_API int nlosgr_forward_project_nc(const float* vol, const float* sensors,
                               int32_t nmeas, int32_t nr, const nlosgr_voxel_grid* grid,
                               const nlosgr_forward_project_opts* opt, float dmin, void* workspace,
                               float* rows_out, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Non-confocal Gaussian renderer (ABI 13, an addition: three new symbols, nothing existing changes): the
+ * histogram nlosgr_render_fwd gives for a confocal capture, for a capture whose measurement p is sensed at
+ * s_p = geo->wall[p] while the laser lights l_p (lasers [nlaser][3], nlaser == nmeas = geo->nwall: one spot per
+ * measurement; nlaser == 1: one spot for the capture), and its backward.  geo holds the tables of the SENSED
+ * points, exactly as for a confocal capture; bin k holds HALF the path, tau_k = geo->r[k], as in the
+ * non-confocal voxel operators.  Rays leave the sensed point: omega_ij = (st_i cp_j, st_i sp_j, ct_i).  With
+ * Delta = l_p - s_p, b^2 = |Delta|^2 and c = omega . Delta, the point of ray omega on the ellipsoid
+ * |x - s| + |x - l| = 2 tau is
+ *     D  = tau - c/2
+ *     d  = (tau^2 - b^2/4) / D = tau + (c tau/2 - b^2/4) / D     distance from s;  x = s + d omega
+ *     dl = 2 tau - d = |x - l|                                   (dl >= D > 0 whenever tau > b/2)
+ * and the histogram is
+ *     hist[p,k] = hscale[p] att[k] sum_ij sin(theta_i) q_pijk sum_g w_g(p) pdf_g(x_pijk)
+ *     q_pijk    = tau_k^2 / (dl D);   q = 0 in bins with tau_k <= b/2 (no such path exists)
+ *     w_g(p)    = sigmoid(opacity_g) max(0, 0.5 + SH_g(dir(mu_g - s_p)))          as nlosgr_render_fwd
+ * (the shell measure d^2 sin(theta) dtheta dphi (dl / D) dtau times the physical falloff 1 / (d^2 dl^2) is
+ * sin(theta) / (dl D); the confocal sin(theta) / tau^2 already sits in att[k], and q is the ratio of the two).
+ * With l_p == s_p: q = 1 and d = tau, the confocal renderer's quantity.
+ *   scope        NLOSGR_MODE_NOOCL, NLOSGR_SELECT_SUPPORT, the histogram only; both presets with every SH degree
+ *                nlosgr_render_fwd takes; cutoff > 0 is culled, cutoff <= 0 dense (every sample; slow, for tests).
+ *   validation   on the host before any launch: another mode, NLOSGR_SELECT_AABB or ray_cache != 0:
+ *                NLOSGR_E_UNSUPPORTED; a non-zero nsplit, g_begin, g_end or flags, a NULL lasers or nlaser not in
+ *                {1, nmeas}: NLOSGR_E_INVALID; otherwise what nlosgr_render_fwd validates, and a NULL hist_out
+ *                (nmeas > 0), output or workspace (ng > 0): NLOSGR_E_INVALID.
+ *   outputs      overwritten.  ng == 0: hist_out is zero-filled, and the backward writes and launches nothing.
+ *                nmeas == 0 is valid (the backward then zero-fills its outputs, as with a NULL grad_hist).  A bin
+ *                with tau_k <= b/2 is exactly 0 and takes no gradient.  d_features is [ng,k_feat] with zero in
+ *                columns >= (sh_degree+1)^2; the other outputs are laid out as nlosgr_render_bwd's.
+ *   determinism  no float atomics.  Two runs are bitwise equal.  Row p of the forward depends on measurement p,
+ *                the Gaussians and opt alone (each bin's sum runs over the Gaussians in ascending index, then the
+ *                rays in (i, j) order): rendering a subset of the measurements gives bitwise those rows.  In the
+ *                backward a Gaussian's five rows depend on that Gaussian, the geometry, the lasers, opt and the
+ *                upstream alone, not on the other Gaussians, ng or the order: permuting the Gaussians permutes
+ *                the rows bitwise.  nlaser == 1 gives bitwise the result of that spot repeated nmeas times.
+ *   one support  the same device functions decide, in both directions and from the same fp32 inputs, a pair's
+ *                cull, its (theta, phi) box, a ray's bin range [kl, kh] (the bins whose d lies in the ray's
+ *                in-support interval; d grows with tau and tau(d) = (d + sqrt(d^2 - 2 d c + b^2)) / 2 inverts it)
+ *                and a bin's validity, so a (p, i, j, k, g) sample is in the backward iff it is in the forward.
+ *                A sample outside is dropped, not multiplied by zero.
+ *   skipped      in culled mode a Gaussian with a non-finite parameter record is skipped (zero rows).  A clamped
+ *                albedo (0.5 + SH < 0) contributes nothing and gets zero feature and mu-through-SH gradient.
+ * The library neither allocates nor synchronises.  Sharding needs nothing here: a slice of geo's rows with the
+ * same rows of lasers is a valid call, and by the determinism clause gives those rows bitwise.
+ * ------------------------------------------------------------------------------------- */
+
+/* Scratch bytes for nlosgr_render_nc_fwd / _bwd (host only; 0 with a message in nlosgr_last_error on invalid input). */
+NLOSGR_API size_t nlosgr_render_nc_workspace_bytes(const nlosgr_gaussians* g, const nlosgr_geometry* geo,
+                                        int32_t nlaser, const nlosgr_options* opt);
+
+/* hist_out [nmeas, nr]. */
+NLOSGR_API int nlosgr_render_nc_fwd(const nlosgr_gaussians* g, const nlosgr_geometry* geo, const float* lasers,
+                         int32_t nlaser, const nlosgr_options* opt, void* workspace, float* hist_out,
+                         void* hip_stream);
+
+/* grad_hist [nmeas, nr] (NULL: the outputs are zero-filled) -> the gradients of the raw parameters. */
+NLOSGR_API int nlosgr_render_nc_bwd(const nlosgr_gaussians* g, const nlosgr_geometry* geo, const float* lasers,
+                         int32_t nlaser, const nlosgr_options* opt, void* workspace, const float* grad_hist,
+                         float* d_mu, float* d_scaling, float* d_rotation, float* d_opacity, float* d_features,
+                         void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

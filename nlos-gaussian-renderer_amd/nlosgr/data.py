@@ -187,6 +187,20 @@ def volume_geometry(data_kwargs, ns, start, end, preset="cuda", mode="noocl"):
                           data_kwargs["deltaT"], float(vp[1]), preset, mode)
 
 
+def volume_geometry_nc(data_kwargs, ns, start, end, preset="cuda"):
+    """(geo, lasers) for the non-confocal Gaussian renderer (nlosgr.render_nc): geo holds build_geometry's tables
+    of the SENSED points in the (shuffled) column order of volume_geometry, lasers is [nmeas, 3] or [1, 3] from
+    backproject.capture_lasers.  A confocal capture returns lasers equal to the sensed points, so one code path
+    serves both kinds of capture."""
+    from .backproject import capture_lasers
+    walls = data_kwargs["camera_grid_positions"].t().contiguous().float()
+    vp = data_kwargs["volume_position"]
+    geo = build_geometry(walls, data_kwargs["volume_box_point"].float(), ns, start, end, data_kwargs["c"],
+                         data_kwargs["deltaT"], float(vp[1]), preset, "noocl")
+    lasers = capture_lasers(data_kwargs)
+    return geo, (walls.clone() if lasers is None else lasers.to(walls.device))
+
+
 def volume_target(data_kwargs, start, num_r):
     """[M*N, num_r] measured histograms nlos_data[I1:I1+num_r, m, n] for every wall point, I1 =
     floor(start) (nlos_helpers.py:153, :323), rows in the same order as volume_geometry."""
