@@ -38,6 +38,8 @@
  *                          (checks a volume against the capture; the least-squares volume)
  *   nlosgr_*_nc         no counterpart: the two voxel operators for a non-confocal capture (laser spot and
  *                          sensed spot differ)
+ *   nlosgr_backproject_phasor  no counterpart: phasor-field reconstruction, the back-projection of complex rows
+ *                          (the capture filtered with a Morlet wavelet) in one pass, and its magnitude
  *   nlosgr_render_nc_*  no counterpart: the Gaussian renderer of such a capture, forward and backward (the
  *                          no-occlusion histogram; nlosgr_render_fwd / _bwd stay confocal)
  */
@@ -665,6 +667,33 @@ NLOSGR_API int nlosgr_forward_project_nc(const float* vol, const float* sensors,
                               int32_t nmeas, int32_t nr, const nlosgr_voxel_grid* grid,
                               const nlosgr_forward_project_opts* opt, float dmin, void* workspace,
                               float* rows_out, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Phasor-field reconstruction (ABI 13, an addition: one new symbol, nothing existing changes): the
+ * back-projection of COMPLEX rows in one pass.  rows_c is [nmeas][nr][2], bin j of measurement i stored as
+ * (re, im): the capture filtered in time with a complex wavelet (the virtual illumination; nlosgr/phasor.py
+ * builds the Morlet wavelet and the rows).  lasers == NULL with nlaser == 0 is a confocal capture and uses
+ * nlosgr_backproject's arithmetic per (voxel, measurement) pair (d-based, so every power matches it); otherwise
+ * lasers is [nlaser][3] with nlaser in {1, nmeas} and the arithmetic is nlosgr_backproject_nc's.
+ *   planes [2][nx][ny][nz]: plane 0 is bitwise what the real entry point gives for the rows' re channel alone,
+ *     plane 1 for the im channel: the coordinate, the clamp into [-2, nr + 1], k, f, the weight and the selects
+ *     that drop out-of-row values are formed once per pair and shared by both channels; each channel is then
+ *     summed under the real entry points' contract (measurements in ascending order, tiles of 256 counted from
+ *     measurement 0, an fp32 sum within a tile started at 0, an fp64 sum across tiles, one rounding to fp32).
+ *     opt->accumulate adds this call's rounded sums into planes.  No atomics: bitwise repeatable, independent of
+ *     bricks; nlaser == 1 gives bitwise the result of that spot repeated nmeas times.  NaN / inf bins reach
+ *     exactly the voxels that sample them, per channel.
+ *   mag [nx][ny][nz] or NULL: (float)sqrt((double)re*re + (double)im*im) of the fp32 plane values as this call
+ *     leaves them (after accumulation), written in the same kernel; NaN where either plane is NaN.
+ *   nmeas == 0: planes is zeroed (left as it is under accumulate) and mag is still the magnitude of planes.
+ *   One 16-byte read per pair at complex bin clamp(k, 0, nr - 2), 8-byte aligned and inside the row (nr == 1: one
+ *     8-byte read): rows_c must be 8-byte aligned.
+ *   Validated on the host before any launch as nlosgr_backproject_nc, plus a NULL planes and an nlaser that does
+ *     not fit lasers (NLOSGR_E_INVALID).
+ * ------------------------------------------------------------------------------------- */
+NLOSGR_API int nlosgr_backproject_phasor(const float* rows_c, const float* sensors, const float* lasers,
+                              int32_t nlaser, int32_t nmeas, int32_t nr, const nlosgr_voxel_grid* grid,
+                              const nlosgr_backproject_opts* opt, float* planes, float* mag, void* hip_stream);
 
 /* ---------------------------------------------------------------------------------------
  * Non-confocal Gaussian renderer (ABI 13, an addition: three new symbols, nothing existing changes): the

@@ -39,35 +39,6 @@ struct BpArgs {
     float* out;
 };
 
-template <int POWER>
-__device__ __forceinline__ float bp_weight(float d) {
-    if (POWER == 0) return 1.0f;
-    if (POWER == 1) return d;
-    const float d2 = d * d;
-    if (POWER == 2) return d2;
-    if (POWER == 3) return d2 * d;
-    return d2 * d2;
-}
-
-// one (voxel, wall point) pair as a BpTap (nlosgr_project.hpp: the two-bin read and its selects)
-// ss = dx*dx + dy*dy (shared by the lane's two voxels); kmax = max(nr - 2, 0)
-template <int POWER>
-__device__ __forceinline__ BpTap bp_tap(float ss, float dz, float r0, float inv_dr, int kmax, float umax) {
-#pragma clang fp contract(off)
-    BpTap t;
-    const float d = fsqrt(ss + dz * dz);
-    // clamped to [-2, nr + 1]: both bins are outside the row at either end (a NaN u goes to -2: no light)
-    const float u = fminf(fmaxf((d - r0) * inv_dr, -2.0f), umax);
-    const float kf = floorf(u);
-    const int k = (int)kf;
-    const int kb = min(max(k, 0), kmax);
-    t.f = u - kf;
-    t.w = bp_weight<POWER>(d);
-    t.ib = 4u * (unsigned)kb;
-    t.e = k - kb;
-    return t;
-}
-
 // wall points [j, j + N) of the staged tile: every bin offset first, then all 2 N reads, then the sums in
 // wall order (the reads of N wall points are in flight together; the order of the additions is the contract's)
 template <int POWER, bool PAIR, int N>

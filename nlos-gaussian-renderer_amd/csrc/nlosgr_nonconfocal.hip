@@ -27,35 +27,8 @@ using namespace nlosgr::detail;
 
 namespace {
 
-// m^(|POWER|/2) from m = dl * ds
-template <int POWER>
-__device__ __forceinline__ float nc_weight(float m) {
-    constexpr int P = POWER < 0 ? -POWER : POWER;
-    if (P == 0) return 1.0f;
-    float p;
-    if (P == 2) p = m;
-    else if (P == 4) p = m * m;
-    else {
-        const float r = fsqrt(m);
-        p = P == 1 ? r : m * r;
-    }
-    return POWER < 0 ? 1.0f / p : p;
-}
-
-// ss = dx*dx + dy*dy of a (voxel column, point) pair
-__device__ __forceinline__ float nc_ss(float x, float y, float px, float py) {
-#pragma clang fp contract(off)
-    const float dx = x - px, dy = y - py;
-    return dx * dx + dy * dy;
-}
-
-__device__ __forceinline__ float nc_dist(float ss, float dz) {
-#pragma clang fp contract(off)
-    return fsqrt(ss + dz * dz);
-}
-
 // ------------------------------------------------------------------------------------------
-// back-projection
+// back-projection (nc_weight, nc_ss, nc_dist, nc_tap, nc_point: nlosgr_project.hpp)
 // ------------------------------------------------------------------------------------------
 struct NcBpArgs {
     const float* rows;
@@ -69,24 +42,6 @@ struct NcBpArgs {
     int accumulate;
     float* out;
 };
-
-// one (voxel, measurement) pair before its bins are read; kmax = max(nr - 2, 0)
-template <int POWER>
-__device__ __forceinline__ BpTap nc_tap(float dl, float ds, float r0, float inv_dr, int kmax, float umax) {
-#pragma clang fp contract(off)
-    BpTap t;
-    const float g = 0.5f * (dl + ds);
-    // clamped to [-2, nr + 1]: both bins are outside the row at either end (a NaN u goes to -2: no light)
-    const float u = fminf(fmaxf((g - r0) * inv_dr, -2.0f), umax);
-    const float kf = floorf(u);
-    const int k = (int)kf;
-    const int kb = min(max(k, 0), kmax);
-    t.f = u - kf;
-    t.w = POWER == 0 ? 1.0f : nc_weight<POWER>(dl * ds);
-    t.ib = 4u * (unsigned)kb;
-    t.e = k - kb;
-    return t;
-}
 
 // measurements [j, j + N) of the staged tile: every bin offset first, then all 2 N reads, then the sums in
 // measurement order.  dl0, dl1: the lane's two laser distances (ONE_LASER)
@@ -121,11 +76,6 @@ __device__ __forceinline__ void nc_bp_step(const float4* stile, const float4* lt
         s0 += bp_eval<POWER>(ta[q], va[q]);
         s1 += bp_eval<POWER>(tb[q], vb[q]);
     }
-}
-
-__device__ __forceinline__ float4 nc_point(const float* p, int i, int n) {
-    return i < n ? make_float4(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2], 0.f)
-                 : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 template <int POWER, bool PAIR, bool ONE_LASER>

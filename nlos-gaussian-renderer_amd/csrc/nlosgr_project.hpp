@@ -1,7 +1,9 @@
 // What the confocal voxel operators (nlosgr_backproject.hip, nlosgr_forward_project.hip) and the non-confocal
-// ones (nlosgr_nonconfocal.hip) share: the back-projection's tile shape and its two-bin read, the forward
-// projector's workspace layout, quantum, max|vol| reduction, finish kernel and split count.  Everything here
-// is the confocal operators' code moved unchanged, so their results are bitwise what they were.
+// ones (nlosgr_nonconfocal.hip) share with each other and with the phasor-field gather (nlosgr_phasor.hip): the
+// back-projection's tile shape, its per-pair arithmetic (bp_tap, nc_tap and their weights) and its two-bin read,
+// the forward projector's workspace layout, quantum, max|vol| reduction, finish kernel and split count.
+// Everything here but the complex read is those operators' code moved unchanged, so their results are bitwise
+// what they were.
 #pragma once
 #include "nlosgr_common.hpp"
 
@@ -53,10 +55,113 @@ __device__ __forceinline__ BpBins bp_read(const char* r, unsigned ib) {
     return v;
 }
 
+// the confocal weight d^POWER
+template <int POWER>
+__device__ __forceinline__ float bp_weight(float d) {
+    if (POWER == 0) return 1.0f;
+    if (POWER == 1) return d;
+    const float d2 = d * d;
+    if (POWER == 2) return d2;
+    if (POWER == 3) return d2 * d;
+    return d2 * d2;
+}
+
+// one (voxel, wall point) pair as a BpTap (the two-bin read and its selects)
+// ss = dx*dx + dy*dy (shared by the lane's two voxels); kmax = max(nr - 2, 0)
+template <int POWER>
+__device__ __forceinline__ BpTap bp_tap(float ss, float dz, float r0, float inv_dr, int kmax, float umax) {
+#pragma clang fp contract(off)
+    BpTap t;
+    const float d = fsqrt(ss + dz * dz);
+    // clamped to [-2, nr + 1]: both bins are outside the row at either end (a NaN u goes to -2: no light)
+    const float u = fminf(fmaxf((d - r0) * inv_dr, -2.0f), umax);
+    const float kf = floorf(u);
+    const int k = (int)kf;
+    const int kb = min(max(k, 0), kmax);
+    t.f = u - kf;
+    t.w = bp_weight<POWER>(d);
+    t.ib = 4u * (unsigned)kb;
+    t.e = k - kb;
+    return t;
+}
+
+// the non-confocal weight m^(|POWER|/2) from m = dl * ds
+template <int POWER>
+__device__ __forceinline__ float nc_weight(float m) {
+    constexpr int P = POWER < 0 ? -POWER : POWER;
+    if (P == 0) return 1.0f;
+    float p;
+    if (P == 2) p = m;
+    else if (P == 4) p = m * m;
+    else {
+        const float r = fsqrt(m);
+        p = P == 1 ? r : m * r;
+    }
+    return POWER < 0 ? 1.0f / p : p;
+}
+
+// ss = dx*dx + dy*dy of a (voxel column, point) pair
+__device__ __forceinline__ float nc_ss(float x, float y, float px, float py) {
+#pragma clang fp contract(off)
+    const float dx = x - px, dy = y - py;
+    return dx * dx + dy * dy;
+}
+
+__device__ __forceinline__ float nc_dist(float ss, float dz) {
+#pragma clang fp contract(off)
+    return fsqrt(ss + dz * dz);
+}
+
+// one (voxel, measurement) pair of a non-confocal capture before its bins are read; kmax = max(nr - 2, 0)
+template <int POWER>
+__device__ __forceinline__ BpTap nc_tap(float dl, float ds, float r0, float inv_dr, int kmax, float umax) {
+#pragma clang fp contract(off)
+    BpTap t;
+    const float g = 0.5f * (dl + ds);
+    // clamped to [-2, nr + 1]: both bins are outside the row at either end (a NaN u goes to -2: no light)
+    const float u = fminf(fmaxf((g - r0) * inv_dr, -2.0f), umax);
+    const float kf = floorf(u);
+    const int k = (int)kf;
+    const int kb = min(max(k, 0), kmax);
+    t.f = u - kf;
+    t.w = POWER == 0 ? 1.0f : nc_weight<POWER>(dl * ds);
+    t.ib = 4u * (unsigned)kb;
+    t.e = k - kb;
+    return t;
+}
+
+// point i of a [n][3] list as a float4 (w unused), zeros past the end
+__device__ __forceinline__ float4 nc_point(const float* p, int i, int n) {
+    return i < n ? make_float4(p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2], 0.f)
+                 : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// the phasor-field gather (nlosgr_phasor.hip): rows of interleaved (re, im) bins.  Both complex bins of a pair
+// come from ONE 16-byte read at complex bin kb (byte offset 2 * BpTap::ib: 8-byte aligned, always inside the
+// row); each channel is then a BpBins for bp_eval
+struct __attribute__((packed, aligned(8))) BpBinsC {
+    float re0, im0, re1, im1;
+};
+
+struct __attribute__((packed, aligned(8))) BpBinC {
+    float re, im;
+};
+
+// PAIR: rows of two or more complex bins, one 16-byte read; a one-bin row reads its bin alone (8 bytes)
+template <bool PAIR>
+__device__ __forceinline__ BpBinsC bp_read_c(const char* r, unsigned ib) {
+    if (PAIR) return *(const BpBinsC*)(r + 2u * ib);
+    const BpBinC b = *(const BpBinC*)r;
+    BpBinsC v;
+    v.re0 = b.re; v.im0 = b.im;
+    v.re1 = 0.0f; v.im1 = 0.0f;
+    return v;
+}
+
 // ------------------------------------------------------------------------------------------
 // forward projection
 // ------------------------------------------------------------------------------------------
-constexpr int kFpRun = 4;                  // voxels adjacent in z that one lane owns per step
+constexpr int kFpRun = 4;                 // voxels adjacent in z that one lane owns per step
 constexpr int kFpStep = kFpRun * kBlock;   // voxels a workgroup covers per step
 constexpr int kFpMaxExtent = 1024;
 constexpr int kFpHeader = 256;             // workspace: [0] the bits of max|vol|; the int64 rows start here

@@ -114,7 +114,7 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_mesh_workspace_bytes", "nlosgr_mesh_count", "nlosgr_mesh_emit", "nlosgr_backproject",
            "nlosgr_forward_project_workspace_bytes", "nlosgr_forward_project",
            "nlosgr_backproject_nc", "nlosgr_forward_project_nc_workspace_bytes", "nlosgr_forward_project_nc",
-           "nlosgr_render_nc_workspace_bytes", "nlosgr_render_nc_fwd", "nlosgr_render_nc_bwd",
+           "nlosgr_backproject_phasor", "nlosgr_render_nc_workspace_bytes", "nlosgr_render_nc_fwd", "nlosgr_render_nc_bwd",
            "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
@@ -210,6 +210,9 @@ def load():
     lib.nlosgr_forward_project_nc.argtypes = [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, PVG, PFP,
                                               ctypes.c_float, _P, _P, _P]
     lib.nlosgr_forward_project_nc.restype = ctypes.c_int
+    lib.nlosgr_backproject_phasor.argtypes = [_P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, PVG,
+                                              ctypes.POINTER(BackprojectOpts), _P, _P, _P]
+    lib.nlosgr_backproject_phasor.restype = ctypes.c_int
     lib.nlosgr_render_nc_workspace_bytes.argtypes = [PG, PGEO, ctypes.c_int32, POPT]
     lib.nlosgr_render_nc_workspace_bytes.restype = ctypes.c_size_t
     lib.nlosgr_render_nc_fwd.argtypes = [PG, PGEO, _P, ctypes.c_int32, POPT, _P, _P, _P]

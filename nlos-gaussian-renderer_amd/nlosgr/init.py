@@ -106,13 +106,15 @@ def sample_from_feasible_space_jittering(args, data_kwargs, margin=0.1, rho_scal
 
 @torch.no_grad()
 def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, device="cuda", start=None, end=None,
-                               power=0, filter="log", gamma=1.0):
+                               power=0, filter="log", gamma=1.0, wavelength=None, cycles=4.0):
     """Data-driven initialisation that does not rest on a first-bounce threshold: init_gaussian_num voxels of
     the capture's back-projection (nlosgr.backproject.backproject_capture on a carving_volume_size^3 grid,
     clamped at 0) drawn with torch.multinomial in proportion to volume**gamma, with replacement, and jittered
     by up to half a grid spacing as the carving sampler does; rho ~ U(0, rho_scale) (numpy), as the other
     two.  Voxels outside the volume box shrunk by `margin` (the rule of init_rand_points) are not drawn.
-    start / end default to args.start / args.end, or the whole capture.  Returns (points [n,3], rho [n,1])."""
+    start / end default to args.start / args.end, or the whole capture.  wavelength: when given, the volume
+    drawn from is the phasor-field magnitude (nlosgr.phasor.phasor_capture with this wavelength and `cycles`;
+    `filter` is then unused) instead of the filtered back-projection.  Returns (points [n,3], rho [n,1])."""
     from .backproject import backproject_capture
     n = args.init_gaussian_num
     rho = np.random.rand(n, 1) * rho_scale
@@ -123,7 +125,11 @@ def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, dev
         if end is None:
             end = data_kwargs["nlos_data"].shape[0]
     res = args.carving_volume_size
-    out = backproject_capture(data_kwargs, res, start, end, power=power, filter=filter, positive=True)
+    if wavelength is None:
+        out = backproject_capture(data_kwargs, res, start, end, power=power, filter=filter, positive=True)
+    else:
+        from .phasor import phasor_capture
+        out = phasor_capture(data_kwargs, res, start, end, wavelength, cycles=cycles, power=power)
     vol, grid = out["volume"], out["grid"]
     dev = vol.device
     pmin, pmax = data_kwargs["pmin"][:3].to(dev), data_kwargs["pmax"][:3].to(dev)
