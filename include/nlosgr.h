@@ -42,6 +42,8 @@
  *                          (the capture filtered with a Morlet wavelet) in one pass, and its magnitude
  *   nlosgr_render_nc_*  no counterpart: the Gaussian renderer of such a capture, forward and backward (the
  *                          no-occlusion histogram; nlosgr_render_fwd / _bwd stay confocal)
+ *   nlosgr_sgld_noise   no counterpart (main.py:163-164, 215-217 leave it as future work): the position noise of
+ *                          3DGS-MCMC's SGLD sampler after an optimizer step, from a counter-based generator
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -755,6 +757,48 @@ NLOSGR_API int nlosgr_render_nc_bwd(const nlosgr_gaussians* g, const nlosgr_geom
                          int32_t nlaser, const nlosgr_options* opt, void* workspace, const float* grad_hist,
                          float* d_mu, float* d_scaling, float* d_rotation, float* d_opacity, float* d_features,
                          void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * SGLD noise step (an addition to ABI 13: one new symbol and one new struct, nothing existing changes): the
+ * position noise of 3DGS-MCMC's sampler, applied after an optimizer step.  Each nearly transparent Gaussian gets a
+ * kick shaped by its own covariance; no counterpart in the reference, which leaves the spot open in both training
+ * loops (main.py:163-164, 215-217).  One thread per Gaussian; rows are independent; no atomics, no LDS, no
+ * workspace, no generator state on the device.  For row i of g, with n = first_index + i:
+ *   words     x0..x3 = Philox4x32-10 (Salmon et al. 2011; multipliers D2511F53, CD9E8D57, key increments 9E3779B9,
+ *             BB67AE85, ten rounds) of the counter (lo32 n, hi32 n, lo32 iteration, hi32 iteration) under the key
+ *             (lo32 seed, hi32 seed).
+ *   uniforms  u_j = ((x_j >> 9) + 0.5) 2^-23: exact in fp32, never 0 or 1.
+ *   normals   xi0 = sqrt(-2 ln u0) cos(2 pi u1), xi1 = sqrt(-2 ln u0) sin(2 pi u1), xi2 = sqrt(-2 ln u2) cos(2 pi u3)
+ *             (Box-Muller; the accurate logf and sqrtf, cos / sin (2 pi u) as cospif / sinpif (2 u): 2 u is exact in
+ *             fp32, so each normal carries a few ulp of its own size, also where the cosine is near zero).
+ *   gate      sigma = sigmoid(opacity_i) as nlosgr_render_fwd forms it;  a = (1 - sigma) - gate_x0;
+ *             gate = 1 / (1 + expf(-gate_k a)): 3DGS-MCMC's op_sigmoid(1 - opacity) with k = 100, x0 = 0.995.  Where
+ *             expf overflows to inf the gate is exactly 0 (never NaN).
+ *   shape     with s~ and R' of the preset / scaling_modifier of `g` exactly as in nlosgr_render_fwd, the Gaussian's
+ *             covariance is Sigma = R'^T diag(s~^2) R' (the inverse of the renderer's N = A^T A), and
+ *             Sigma xi = R'^T (s~^2 o (R' xi)); Sigma itself is not formed.  Sigma, not its square root: 3DGS-MCMC's
+ *             own rule.
+ *   result    delta = (scale gate) (Sigma xi), rounded to fp32, then mu_out[i] = mu[i] + delta in one fp32 addition
+ *             (no fma of the two), and noise_out[i] = delta when given: mu + noise_out == mu_out bitwise.
+ * The result is a function of (seed, iteration, n) and row i alone: two runs are bitwise equal; a slice of the rows
+ * with first_index moved along gives bitwise those rows; every rank that holds the same Gaussians computes the same
+ * values, so a wall shard exchanges nothing for it.  mu_out may alias g->mu (each thread reads its row before it
+ * writes it).  A non-finite parameter makes that Gaussian's own row non-finite and no other.  sh_degree, k_feat and
+ * features of `g` are not read.
+ * ng == 0 is valid and launches nothing.  NLOSGR_E_INVALID: a null struct, ng < 0, an unknown preset and, when
+ * ng > 0, a null mu, scaling, rotation, opacity or mu_out.  The library neither allocates nor synchronises.
+ * ------------------------------------------------------------------------------------- */
+typedef struct nlosgr_sgld {
+    uint64_t seed;        /* Philox key */
+    int64_t  iteration;   /* Philox counter words 2,3 */
+    int64_t  first_index; /* index of row 0 of g in the whole model: counter words 0,1 = first_index + i */
+    float    scale;       /* noise_lr * lr_mu, formed in double by the caller */
+    float    gate_k, gate_x0;   /* 3DGS-MCMC: 100, 0.995 */
+} nlosgr_sgld;
+
+NLOSGR_API int nlosgr_sgld_noise(const nlosgr_gaussians* g, const nlosgr_sgld* o,
+                      float* mu_out /* [ng,3], may alias g->mu */,
+                      float* noise_out /* [ng,3] or NULL */, void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

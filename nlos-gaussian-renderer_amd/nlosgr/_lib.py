@@ -85,6 +85,11 @@ class ForwardProjectOpts(ctypes.Structure):
                 ("accumulate", ctypes.c_int32), ("nsplit", ctypes.c_int32)]
 
 
+class Sgld(ctypes.Structure):
+    _fields_ = [("seed", ctypes.c_uint64), ("iteration", ctypes.c_int64), ("first_index", ctypes.c_int64),
+                ("scale", ctypes.c_float), ("gate_k", ctypes.c_float), ("gate_x0", ctypes.c_float)]
+
+
 ADAM_MAX_GROUPS = 8  # NLOSGR_ADAM_MAX_GROUPS
 MAX_PER_RAY = 256   # NLOSGR_MAX_PER_RAY
 IRF_MAX_TAPS = 512  # NLOSGR_IRF_MAX_TAPS
@@ -115,7 +120,7 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_forward_project_workspace_bytes", "nlosgr_forward_project",
            "nlosgr_backproject_nc", "nlosgr_forward_project_nc_workspace_bytes", "nlosgr_forward_project_nc",
            "nlosgr_backproject_phasor", "nlosgr_render_nc_workspace_bytes", "nlosgr_render_nc_fwd", "nlosgr_render_nc_bwd",
-           "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
+           "nlosgr_sgld_noise", "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
 _load_error = None
@@ -219,6 +224,8 @@ def load():
     lib.nlosgr_render_nc_fwd.restype = ctypes.c_int
     lib.nlosgr_render_nc_bwd.argtypes = [PG, PGEO, _P, ctypes.c_int32, POPT, _P, _P, _P, _P, _P, _P, _P, _P]
     lib.nlosgr_render_nc_bwd.restype = ctypes.c_int
+    lib.nlosgr_sgld_noise.argtypes = [PG, ctypes.POINTER(Sgld), _P, _P, _P]
+    lib.nlosgr_sgld_noise.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

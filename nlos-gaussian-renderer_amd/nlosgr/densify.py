@@ -136,4 +136,20 @@ def prune_dead_mask(model, min_opacity=0.005):
     return (model.get_opacity <= min_opacity).reshape(-1)
 
 
-__all__ = ["compute_relocation", "relocate_gs", "add_new_gs", "prune_dead_mask", "N_MAX"]
+def mcmc_control(step, from_iter=500, until_iter=25_000, interval=100, cap_max=100_000, min_opacity=0.005):
+    """The density-control schedule of the training loop (main.py:243-247) for a train step (TrainStep,
+    VoxelFitStep, NcTrainStep), called after the step: when from_iter < step.iteration < until_iter and
+    step.iteration is a multiple of interval (step.iteration counts the finished steps, as current_iter does
+    there), the dead Gaussians (opacity <= min_opacity) are relocated and the set grows by 5 % up to cap_max, both
+    with train_step=step so its Adam state follows.  Returns the number of Gaussians added, or None when the
+    schedule did not fire."""
+    it = int(step.iteration)
+    if int(interval) < 1:
+        raise ValueError("nlosgr: mcmc_control needs interval >= 1")
+    if not (from_iter < it < until_iter and it % int(interval) == 0):
+        return None
+    relocate_gs(step.model, prune_dead_mask(step.model, min_opacity), train_step=step)
+    return add_new_gs(step.model, cap_max, train_step=step)
+
+
+__all__ = ["compute_relocation", "relocate_gs", "add_new_gs", "prune_dead_mask", "mcmc_control", "N_MAX"]

@@ -30,7 +30,8 @@ from . import _lib
 from .backproject import _lasers_arg
 from .loss import loss as fused_loss
 from .render import RenderConfig, _as_f32, _structs
-from .train import Adam, OptimizationParams, TrainStep
+from .train import (Adam, OptimizationParams, TrainStep, add_mcmc_arguments, check_mcmc_arguments, mcmc_options,
+                    run_steps)
 
 
 def lasers_for(lasers, geo, what="render_nc"):
@@ -154,6 +155,7 @@ class NcTrainStep:
     # TrainStep's own: the schedule, the density-control hook, and regulariser + keep_grads + Adam + SH schedule
     learning_rates = TrainStep.learning_rates
     rebind = TrainStep.rebind
+    _activation = TrainStep._activation
     _finish = TrainStep._finish
 
     @torch.no_grad()
@@ -188,11 +190,13 @@ def parse_args(argv=None):
     ap.add_argument("--resolution", type=int, default=64, help="grid of the back-projection the Gaussians start from")
     ap.add_argument("--loss", choices=sorted(_lib.LOSSES), default="mse")
     ap.add_argument("--out", required=True, help="checkpoint to write")
+    add_mcmc_arguments(ap)
     a = ap.parse_args(argv)
     if a.end <= a.start:
         ap.error("--end must be greater than --start")
     if a.iterations < 1:
         ap.error("--iterations must be >= 1")
+    check_mcmc_arguments(ap, a)
     if a.gaussians < 1:
         ap.error("--gaussians must be >= 1")
     if a.ns < 1:
@@ -220,7 +224,7 @@ def main(argv=None):
     geo, lasers = volume_geometry_nc(dk, a.ns, a.start, a.end, preset="cuda")
     target = volume_target(dk, a.start, geo.nr)
     cfg = RenderConfig(preset="cuda", mode="noocl", cutoff=a.cutoff, c_deltaT=float(dk["c"]) * float(dk["deltaT"]))
-    step = NcTrainStep(model, geo, lasers, cfg, target, irf=dk.get("irf"), loss=a.loss)
+    step = NcTrainStep(model, geo, lasers, cfg, target, irf=dk.get("irf"), loss=a.loss, opt=mcmc_options(a))
     # one least-squares gain between the initial render and the capture (one host read)
     from . import features_flat
     pred = render_nc_forward(model._mu, model._scaling, model._rotation, model._opacity, features_flat(model), geo,
@@ -229,9 +233,9 @@ def main(argv=None):
     num = float((pred.double() * target.double()).sum())
     if den > 0 and num > 0:
         step.gt_times = num / den
-    losses = torch.stack([step()[0] for _ in range(a.iterations)]).cpu().numpy()
+    losses = run_steps(step, a).cpu().numpy()
     save_checkpoint(a.out, model, train_step=step)
-    print(f"wrote {a.out}: {a.gaussians} Gaussians, {geo.nwall} measurements x {geo.nr} bins [{a.start}, {a.end}), "
+    print(f"wrote {a.out}: {model._mu.shape[0]} Gaussians, {geo.nwall} measurements x {geo.nr} bins [{a.start}, {a.end}), "
           f"{a.ns} x {a.ns} rays, cutoff {a.cutoff:g}, {a.iterations} iterations, loss {losses[0]:.6g} -> "
           f"{losses[-1]:.6g}")
 

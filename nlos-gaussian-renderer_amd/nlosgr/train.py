@@ -12,6 +12,7 @@ host synchronisation inside the step:
                                                       nlosgr_loss_irf for the photon-count likelihood]
     ->  render_backward (HIP, walks the ray cache)  ->  [one packed all-reduce when sharded]
     ->  nlosgr_adam (all six groups in one launch; position lr from get_expon_lr_func)
+    ->  [nlosgr_sgld_noise when opt.noise_lr > 0: the SGLD position noise of 3DGS-MCMC, off by default]
 
 The returned loss is a device tensor; reading it is the caller's choice (and its only sync).
 """
@@ -63,6 +64,11 @@ class OptimizationParams:
     regularization: bool = False     # configs/default.py:88-90, applied in learn_one_iter (main.py:204-208)
     scale_reg: float = 0.01
     opacity_reg: float = 0.01
+    # SGLD position noise after Adam (sgld_noise; 3DGS-MCMC trains with noise_lr = 5e5).  0: no call at all.
+    noise_lr: float = 0.0
+    noise_seed: int = 0
+    noise_gate_k: float = 100.0
+    noise_gate_x0: float = 0.995
 
 
 def mse(hist, target, gt_times=1.0, grad_scale=1.0, want_grad=True, raw=False, irf=None):
@@ -243,6 +249,79 @@ class Adam:
                                    float(self.betas[1]), float(self.eps), _lib.stream_handle(self.params[0].device)))
 
 
+@torch.no_grad()
+def sgld_noise(model, lr_mu, noise_lr, iteration, seed=0, preset="torch", scaling_modifier=1.0, gate_k=100.0,
+               gate_x0=0.995, g_range=None, want_noise=False):
+    """The SGLD step of 3DGS-MCMC on model._mu, in place (nlosgr_sgld_noise; include/nlosgr.h has the arithmetic):
+
+        mu_g += (noise_lr * lr_mu) * sigmoid(gate_k ((1 - sigma_g) - gate_x0)) * Sigma_g xi_g
+
+    Sigma_g is the covariance the renderer gives Gaussian g under preset / scaling_modifier, xi_g three standard
+    normals from Philox4x32-10 keyed by (seed, iteration, g): no generator state, and every rank that holds the
+    same Gaussians adds the same noise.  g_range=(g0, g1) touches rows [g0, g1) alone, with the values the whole
+    call gives them.  Returns the added noise [rows, 3] when want_noise, else None.  One launch, no host
+    synchronisation."""
+    if preset not in _lib.PRESETS:
+        raise ValueError(f"nlosgr: preset must be one of {tuple(_lib.PRESETS)}")
+    lib = _lib.load()
+    ng = model._mu.shape[0]
+    g0, g1 = (0, ng) if g_range is None else (int(g_range[0]), int(g_range[1]))
+    if not 0 <= g0 <= g1 <= ng:
+        raise ValueError(f"nlosgr: g_range must satisfy 0 <= g0 <= g1 <= {ng}")
+    mu = model._mu.data
+    if mu.dtype != torch.float32 or not mu.is_contiguous() or not mu.is_cuda:
+        raise ValueError("nlosgr: sgld_noise needs a contiguous float32 GPU _mu (there is no CPU fallback)")
+    dev = mu.device
+    rows = [mu[g0:g1]] + [t.detach().reshape(ng, w)[g0:g1].to(device=dev, dtype=torch.float32).contiguous()
+                          for t, w in ((model._scaling, 3), (model._rotation, 4), (model._opacity, 1))]
+    g = _lib.Gaussians(g1 - g0, 0, 0, _lib.PRESETS[preset], float(scaling_modifier), _lib.ptr(rows[0]),
+                       _lib.ptr(rows[1]), _lib.ptr(rows[2]), _lib.ptr(rows[3]), None)
+    o = _lib.Sgld(int(seed) & 0xFFFFFFFFFFFFFFFF, int(iteration), g0, float(noise_lr) * float(lr_mu), float(gate_k),
+                  float(gate_x0))
+    noise = torch.empty(g1 - g0, 3, dtype=torch.float32, device=dev) if want_noise else None
+    _lib.check(lib.nlosgr_sgld_noise(ctypes.byref(g), ctypes.byref(o), _lib.ptr(rows[0]), _lib.ptr(noise),
+                                     _lib.stream_handle(dev)))
+    return noise
+
+
+def add_mcmc_arguments(ap):
+    """The SGLD noise and density-control flags of the fitting command lines; the defaults switch both off."""
+    ap.add_argument("--noise-lr", type=float, default=0.0,
+                    help="SGLD position noise after each Adam step (3DGS-MCMC trains with 5e5); 0: off")
+    ap.add_argument("--noise-seed", type=int, default=0, help="seed of the noise's counter-based generator")
+    ap.add_argument("--densify-interval", type=int, default=0,
+                    help="MCMC density control (relocate dead Gaussians, grow by 5 %%) every this many steps; 0: off")
+    ap.add_argument("--densify-from", type=int, default=500, help="density control only after this iteration")
+    ap.add_argument("--densify-until", type=int, default=25_000, help="density control only before this iteration")
+    ap.add_argument("--cap-max", type=int, default=100_000, help="density control grows the set up to this many")
+
+
+def check_mcmc_arguments(ap, a):
+    if not (a.noise_lr >= 0 and math.isfinite(a.noise_lr)):
+        ap.error("--noise-lr must be finite and >= 0")
+    if a.densify_interval < 0:
+        ap.error("--densify-interval must be >= 0")
+    if a.cap_max < 1:
+        ap.error("--cap-max must be >= 1")
+
+
+def mcmc_options(a):
+    """The OptimizationParams of a command line's flags: None (the step's default) when the noise is off."""
+    return OptimizationParams(noise_lr=a.noise_lr, noise_seed=a.noise_seed) if a.noise_lr > 0 else None
+
+
+def run_steps(step, a):
+    """a.iterations calls of `step`, with densify.mcmc_control after each when --densify-interval is set; the
+    device [iterations] losses."""
+    from .densify import mcmc_control
+    losses = []
+    for _ in range(a.iterations):
+        losses.append(step()[0])
+        if a.densify_interval > 0:
+            mcmc_control(step, a.densify_from, a.densify_until, a.densify_interval, a.cap_max)
+    return torch.stack(losses)
+
+
 class TrainStep:
     """One fused training iteration per call (see module docstring).
 
@@ -319,6 +398,12 @@ class TrainStep:
             for i, (a, b) in enumerate(zip(exp_avg, exp_avg_sq)):
                 self.adam.exp_avg[i].copy_(a.reshape(self._tensors[i].shape))
                 self.adam.exp_avg_sq[i].copy_(b.reshape(self._tensors[i].shape))
+
+    def _activation(self):
+        """(preset, scaling_modifier) the step renders with: a VoxelFitStep carries them itself, the render steps
+        in their cfg."""
+        cfg = getattr(self, "cfg", None)
+        return (cfg.preset, cfg.scaling_modifier) if cfg is not None else (self.preset, self.scaling_modifier)
 
     def learning_rates(self, iteration):
         o = self.opt
@@ -508,7 +593,13 @@ class TrainStep:
             loss2 = torch.stack([loss2[0] + reg, loss2[1]])
         if self.keep_grads:
             self.grads = [g.clone() for g in grads]
-        self.adam.step(grads, self.learning_rates(it))
+        lrs = self.learning_rates(it)
+        self.adam.step(grads, lrs)
+        if self.opt.noise_lr > 0:
+            # replicated quantities in, the same noise out on every rank of a wall shard: nothing is exchanged
+            preset, mod = self._activation()
+            sgld_noise(m, lrs[0], self.opt.noise_lr, it, seed=self.opt.noise_seed, preset=preset,
+                       scaling_modifier=mod, gate_k=self.opt.noise_gate_k, gate_x0=self.opt.noise_gate_x0)
         self.iteration = it + 1
         if self.sh_schedule and self.iteration % 1000:   # main.py:240-241 (fires when NOT a multiple)
             m.oneupSHdegree()

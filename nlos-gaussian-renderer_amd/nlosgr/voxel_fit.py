@@ -28,7 +28,8 @@ from . import _lib
 from .backproject import _gpu_f32, _lasers_arg, backproject, capture_lasers
 from .forward_project import forward_project
 from .loss import loss as fused_loss
-from .train import Adam, OptimizationParams, TrainStep
+from .train import (Adam, OptimizationParams, TrainStep, add_mcmc_arguments, check_mcmc_arguments, mcmc_options,
+                    run_steps)
 from .voxelize import VoxelGrid, front_view, voxelize, voxelize_backward
 
 SH_C0 = 0.28209479177387814
@@ -105,6 +106,7 @@ class VoxelFitStep:
     # TrainStep's own: the schedule, the density-control hook, and regulariser + keep_grads + Adam + SH schedule
     learning_rates = TrainStep.learning_rates
     rebind = TrainStep.rebind
+    _activation = TrainStep._activation
     _finish = TrainStep._finish
 
     def project(self, volume):
@@ -195,12 +197,14 @@ def parse_args(argv=None):
     ap.add_argument("--cutoff", type=float, default=3.0, help="Mahalanobis support radius; <= 0: dense")
     ap.add_argument("--loss", choices=sorted(_lib.LOSSES), default="mse")
     ap.add_argument("--out", required=True, help="checkpoint to write")
+    add_mcmc_arguments(ap)
     ap.add_argument("--recon", default=None, help="also write the fitted Gaussians' voxel volume (nlosgr.voxelize keys)")
     a = ap.parse_args(argv)
     if a.end <= a.start:
         ap.error("--end must be greater than --start")
     if a.iterations < 1:
         ap.error("--iterations must be >= 1")
+    check_mcmc_arguments(ap, a)
     if a.gaussians < 1:
         ap.error("--gaussians must be >= 1")
     if a.resolution < 2:
@@ -224,15 +228,15 @@ def main(argv=None):
     spacing = float(dk["volume_size"]) / (a.resolution - 1)
     model = model_from_points(pts, rho, spacing)
     step = fit_capture(dk, model, a.resolution, a.start, a.end, power=a.power, falloff=a.falloff, preset="cuda",
-                       cutoff=a.cutoff, loss=a.loss)
+                       cutoff=a.cutoff, loss=a.loss, opt=mcmc_options(a))
     # one least-squares gain between A(albedo_density) and the rows, from the initial Gaussians (one host read)
     pred = step.project(voxelize(model, step.grid, step.cam, preset="cuda", cutoff=a.cutoff, want_density=False)[1])
     den = float(pred.double().square().sum())
     if den > 0:
         step.volume_scale = float((pred.double() * step.rows.double()).sum()) / den
-    losses = torch.stack([step()[0] for _ in range(a.iterations)]).cpu().numpy()
+    losses = run_steps(step, a).cpu().numpy()
     save_checkpoint(a.out, model, train_step=step)
-    print(f"wrote {a.out}: {a.gaussians} Gaussians, {step.grid.shape} voxels, bins [{a.start}, {a.end}), power "
+    print(f"wrote {a.out}: {model._mu.shape[0]} Gaussians, {step.grid.shape} voxels, bins [{a.start}, {a.end}), power "
           f"{a.power}, falloff {a.falloff:g}, {a.iterations} iterations, loss {losses[0]:.6g} -> {losses[-1]:.6g}")
     if a.recon:
         dens, alb = voxelize(model, step.grid, step.cam, preset="cuda", cutoff=a.cutoff)
