@@ -8,7 +8,7 @@ exp(2 pi i t / P)), the complex rows are back-projected, and the image is the ma
     P(x) = sum_i weight ((1-f) y_i[k] + f y_i[k+1])                phasor_backproject: nlosgr_backproject_phasor
     volume(x) = |P(x)|
 
-The gather is one HIP pass over interleaved (re, im) rows (csrc/nlosgr_phasor.hip): the per-pair arithmetic of
+The gather is one HIP pass over interleaved (re, im) rows (csrc/nlosgr_backproject.hip): the per-pair arithmetic of
 backproject (lasers=None) or of its non-confocal form (lasers=) formed once and shared by both channels, one
 16-byte read per (voxel, measurement) pair.  Each plane is bitwise what backproject gives for that channel alone.
 On noisy or non-confocal data the image is much cleaner than filtered back-projection, because the wavelet is a

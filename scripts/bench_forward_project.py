@@ -4,19 +4,15 @@ C3's window (1024 bins of c deltaT = 1.28 / 1024 from bin 128), for a dense stan
 wall points (cdist, floor, scatter_add_; written below; timed on the first --torch-walls wall points and
 scaled to the wall, since its time is linear in them), and (b) nlosgr_backproject on the same counts (the
 adjoint does the same pair arithmetic with gathers in place of the scatter's LDS adds).  --ab LIB times the HIP
-kernel of an alternative in-tree build as well (a child process started before this one touches the GPU): the
-build with run merging, the one whose workgroups serve one wall point each, and the two timing-only builds
-(wrong rows) without the LDS adds and without the fp32 -> int64 conversion:
+kernel of an alternative in-tree build as well (a child process started before this one touches the GPU), e.g. the
+parent commit's library built from a worktree of it:
 
-    python nlos-gaussian-renderer_amd/build.py --out ab/libnlosgr_merge.so -D NLOSGR_FP_MERGE
-    python nlos-gaussian-renderer_amd/build.py --out ab/libnlosgr_onewall.so -D NLOSGR_FP_ONEWALL
-    python nlos-gaussian-renderer_amd/build.py --out ab/libnlosgr_noadd.so -D NLOSGR_FP_TIMING=1
-    python nlos-gaussian-renderer_amd/build.py --out ab/libnlosgr_nocvt.so -D NLOSGR_FP_TIMING=2
+    python nlos-gaussian-renderer_amd/build.py --out $OLDPWD/ab/libnlosgr_parent.so
 
 Warm-up, timed repeats, device-event timing (as scripts/bench_backproject.py); writes one JSON file.
 
     python scripts/bench_forward_project.py [--out profiles/forward_project_c3.json] [--repeats 5] [--power 0]
-        [--ab ab/libnlosgr_merge.so --ab ab/libnlosgr_onewall.so ...]
+        [--ab ab/libnlosgr_parent.so ...]
 """
 import argparse
 import json

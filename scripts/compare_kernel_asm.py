@@ -1,7 +1,7 @@
-"""Compare the machine code of every kernel between two sets of gfx950 device assemblies (a source refactor
+r"""Compare the machine code of every kernel between two sets of gfx950 device assemblies (a source refactor
 must leave each kernel's instructions as they were).
 
-    python scripts/compare_kernel_asm.py OLD.s [OLD2.s ...] --new NEW.s [NEW2.s ...] [-v]
+    python scripts/compare_kernel_asm.py OLD.s [OLD2.s ...] --new NEW.s [NEW2.s ...] [--rename REGEX=REPL ...] [-v]
 
 The .s files are device-only assemblies, one per source file, made with build.py's flags:
 
@@ -10,7 +10,13 @@ The .s files are device-only assemblies, one per source file, made with build.py
 Kernels are matched by demangled name with namespace qualifiers removed.  A body runs from the kernel's
 label to its .Lfunc_end; before the comparison ';' comments and blank lines are dropped, the per-file
 function index in .LBB<n>_ and .Lfunc_end<n> is removed, and mangled names inside a body (a kernel that
-names itself or a device global) are reduced in the same way as the kernel names.  Prints the kernels
+names itself or a device global) are reduced in the same way as the kernel names.  --rename REGEX=REPL
+(re.sub, may be repeated, applied in order) rewrites the OLD side's plain names (of the kernels and inside their bodies), so that a kernel the refactor
+renamed is paired with its successor, e.g.
+
+    --rename 'backproject_kernel<(-?\d+), (\w+)>\(BpArgs\)=gather_kernel<\1, \2, 0, 1>(GatherArgs)'
+
+Prints the kernels
 only one side has and those whose bodies differ (-v: a unified diff of each); exit status 1 if any.
 """
 import difflib
@@ -63,12 +69,22 @@ def kernels(path):
 def main():
     args = [a for a in sys.argv[1:] if a != "-v"]
     verbose = "-v" in sys.argv[1:]
+    renames = []
+    while "--rename" in args:
+        i = args.index("--rename")
+        rx, _, repl = args[i + 1].partition("=")
+        renames.append((re.compile(rx), repl))
+        del args[i:i + 2]
     if "--new" not in args:
         sys.exit(__doc__)
     cut = args.index("--new")
     old, new = {}, {}
     for p in args[:cut]:
-        old.update(kernels(p))
+        for name, body in kernels(p).items():
+            for rx, repl in renames:    # the body names its kernel too (descriptor, section)
+                name, body = rx.sub(repl, name), [rx.sub(repl, ln) for ln in body]
+            assert name not in old or old[name] == body, f"{p}: two old kernels named {name}"
+            old[name] = body
     for p in args[cut + 1:]:
         for name, body in kernels(p).items():
             # a template kernel of a shared header may be emitted by several files: the copies must agree

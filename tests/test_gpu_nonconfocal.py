@@ -1,5 +1,6 @@
 """GPU checks of the non-confocal back-projection and forward projection (include/nlosgr.h, csrc/
-nlosgr_nonconfocal.hip) against the float64 oracle of tests/nonconfocal_oracle.py: |gpu - oracle| <= B per voxel
+nlosgr_backproject.hip, csrc/nlosgr_forward_project.hip) against the float64 oracle of
+tests/nonconfocal_oracle.py: |gpu - oracle| <= B per voxel
 or bin, with B the oracle's derived bound and no further factor, and bitwise against the confocal entry points
 where the laser spots are the sensed points.  `-s` prints the worst measured e/B per case.
 

@@ -1,5 +1,5 @@
 """GPU checks of the phasor-field reconstruction (include/nlosgr.h nlosgr_backproject_phasor, csrc/
-nlosgr_phasor.hip, nlosgr/phasor.py).  The reference for the planes is the existing real kernels: plane c is
+nlosgr_backproject.hip, nlosgr/phasor.py).  The reference for the planes is the existing real kernels: plane c is
 BITWISE backproject() of channel c alone, so no tolerance is new here; each plane is also held to the float64
 oracles' derived bound B (no factor), and mag to 1 fp32 ulp of float32(sqrt(float64(re)^2 + float64(im)^2)).
 
