@@ -44,6 +44,7 @@
  *                          no-occlusion histogram; nlosgr_render_fwd / _bwd stay confocal)
  *   nlosgr_sgld_noise   no counterpart (main.py:163-164, 215-217 leave it as future work): the position noise of
  *                          3DGS-MCMC's SGLD sampler after an optimizer step, from a counter-based generator
+ *   nlosgr_fk_*         no counterpart: f-k migration of a confocal capture, the three passes around its two FFTs
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -799,6 +800,46 @@ typedef struct nlosgr_sgld {
 NLOSGR_API int nlosgr_sgld_noise(const nlosgr_gaussians* g, const nlosgr_sgld* o,
                       float* mu_out /* [ng,3], may alias g->mu */,
                       float* noise_out /* [ng,3] or NULL */, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * f-k migration of a confocal capture (an addition to ABI 13: three new symbols, nothing existing changes): Lindell,
+ * Wetzstein, O'Toole 2019.  No counterpart in the reference.  The transform is
+ *     rows -> amplitude -> zero-padded 3-D FFT -> Stolt resampling -> inverse FFT -> |.|^2
+ * on the capture's own (wall point x time bin) lattice, O(N^3 log N) against the O(N^5) of a back-projection.  The two
+ * FFTs are the caller's (the library links the HIP runtime alone); the three symbols are the passes around them.
+ *
+ * Input: rows [H W][nr]; lattice point (m, n), 0 <= m < H, 0 <= n < W, is measured at (xs[n], y0, zs[m]) with uniform
+ * spacings sx, sz, and its row is rows[perm[m stride_m + n stride_n]] (perm NULL: rows[m stride_m + n stride_n]; the
+ * strides are (W, 1) when x runs along the wall's fast index and (1, H) when it runs along the slow one).  r0: radius
+ * of bin 0, dr: bin width, both in half-path units.  Nz = 2 H, Nx = 2 W, Nt = 2 nr; the work arrays are complex64
+ * [Nz][Nx][Nt], interleaved (re, im).
+ *   1 load    psi[m][n][j] = max(rows[v][j], 0) (r0 + j dr)^power, power 0..4 (4: the r^-4 falloff of the renderer's
+ *             histograms); with `amplitude` its square root.  pad = psi at [0:H][0:W][0:nr] of a zero array; the
+ *             padding is zero-filled in the same pass.
+ *   2         S = the unnormalised forward 3-D DFT of pad, exp(-2 pi i ...) (numpy's fftn).
+ *   3 stolt   with signed DFT indices c (z), b (x), a (time), gx = Nt dr / (Nx sx), gz = Nt dr / (Nz sz):
+ *                 src = sqrt(a^2 + (gx b)^2 + (gz c)^2),  k = floor(src),  f = src - k
+ *                 V[c][b][a] = ((1-f) S[c][b][k] + f S[c][b][k+1]) (a / src) exp(-2 pi i (src - a) (r0 / dr) / Nt)
+ *             where a > 0 and k + 1 <= Nt/2 - 1;  V = 0 everywhere else (a <= 0, or a source beyond the positive band),
+ *             written in the same pass.  The phase factor lets a window start at bin I1 > 0 without I1 bins of padding
+ *             in front: it moves the input window back by r0 and the output depth forward by r0.
+ *   4         o = the inverse 3-D DFT of V with the 1/N normalisation (numpy's ifftn).
+ *   5 store   volume[n][j][m] = |o[m][n][j]|^2 for m < H, n < W, j < nr: [nx = W][ny = nr][nz = H] in the voxel order
+ *             (ix ny + iy) nz + iz of nlosgr_voxel_grid; voxel (n, j, m) is the point (xs[n], y0 + r0 + j dr, zs[m]).
+ * Each pass reads and writes its array once, without atomics; every element is written by one lane from the inputs
+ * alone: bitwise repeatable.  Arithmetic: csrc/nlosgr_fk.hip.  The migrated spectrum must not alias the spectrum.
+ * Validated on the host before any launch (NLOSGR_E_INVALID, text in the last-error string): H, W or nr outside
+ * 1..1024, power outside 0..4, dr <= 0 or not finite, r0 < 0 or not finite, sx or sz <= 0, strides that leave
+ * [0, H W), a null or misaligned pointer (perm may be NULL).  The library neither allocates nor synchronises.
+ * ------------------------------------------------------------------------------------- */
+NLOSGR_API int nlosgr_fk_load(const float* rows /* [H W][nr] */, const int32_t* perm /* [H W] or NULL */, int32_t H,
+                   int32_t W, int32_t nr, int32_t stride_m, int32_t stride_n, float r0, float dr, int32_t power,
+                   int32_t amplitude, float* pad /* [2H][2W][2nr][2], 16-byte aligned */, void* hip_stream);
+NLOSGR_API int nlosgr_fk_stolt(const float* spec /* [2H][2W][2nr][2] */, int32_t H, int32_t W, int32_t nr, float sx,
+                    float sz, float r0, float dr, float* out /* [2H][2W][2nr][2], 16-byte aligned */,
+                    void* hip_stream);
+NLOSGR_API int nlosgr_fk_store(const float* field /* [2H][2W][2nr][2] */, int32_t H, int32_t W, int32_t nr,
+                    float* volume /* [W][nr][H] */, void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

@@ -16,6 +16,7 @@ Layers:
     nlosgr.mesh            surface output: isosurface of a voxelized field as a triangle mesh, PLY export
     nlosgr.backproject     the capture on a voxel grid: back-projection, time filters, backproject_capture
     nlosgr.phasor          phasor-field reconstruction: complex back-projection in one pass, phasor_capture
+    nlosgr.fk              f-k migration of a confocal capture: three HIP passes around torch.fft, fk_capture
     nlosgr.forward_project its adjoint: voxel grid -> transients, voxel_transient, operator_norm, landweber
                            (both take lasers= for a non-confocal capture: the laser spot differs from the sensed one)
     nlosgr.irf             temporal instrument response: IRF, gaussian_irf, convolve_time (render -> capture)
@@ -29,10 +30,12 @@ from .render import RenderConfig, RenderFn, bboxes, render, render_backward, ren
 __all__ = ["Geometry", "build_geometry", "relay_wall_grid", "volume_box_point", "GaussianParams",
            "features_flat", "RenderConfig", "RenderFn", "render", "render_forward", "render_backward", "bboxes",
            "Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply",
-           "backproject_capture", "time_filter", "phasor_capture", "phasor_kernel"]
+           "backproject_capture", "time_filter", "phasor_capture", "phasor_kernel",
+           "fk_capture", "fk_migrate"]
 
 _BP_NAMES = ("backproject_capture", "time_filter")
 _PH_NAMES = ("phasor_capture", "phasor_kernel")
+_FK_NAMES = ("fk_capture", "fk_migrate")
 _MESH_NAMES = ("Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply")
 
 
@@ -49,4 +52,7 @@ def __getattr__(name):
     if name in _PH_NAMES:
         from . import phasor
         return getattr(phasor, name)
+    if name in _FK_NAMES:
+        from . import fk
+        return getattr(fk, name)
     raise AttributeError(f"module 'nlosgr' has no attribute {name!r}")

@@ -120,7 +120,7 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_forward_project_workspace_bytes", "nlosgr_forward_project",
            "nlosgr_backproject_nc", "nlosgr_forward_project_nc_workspace_bytes", "nlosgr_forward_project_nc",
            "nlosgr_backproject_phasor", "nlosgr_render_nc_workspace_bytes", "nlosgr_render_nc_fwd", "nlosgr_render_nc_bwd",
-           "nlosgr_sgld_noise", "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
+           "nlosgr_sgld_noise", "nlosgr_fk_load", "nlosgr_fk_stolt", "nlosgr_fk_store", "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
 _load_error = None
@@ -226,6 +226,13 @@ def load():
     lib.nlosgr_render_nc_bwd.restype = ctypes.c_int
     lib.nlosgr_sgld_noise.argtypes = [PG, ctypes.POINTER(Sgld), _P, _P, _P]
     lib.nlosgr_sgld_noise.restype = ctypes.c_int
+    I32, F32 = ctypes.c_int32, ctypes.c_float
+    lib.nlosgr_fk_load.argtypes = [_P, _P, I32, I32, I32, I32, I32, F32, F32, I32, I32, _P, _P]
+    lib.nlosgr_fk_load.restype = ctypes.c_int
+    lib.nlosgr_fk_stolt.argtypes = [_P, I32, I32, I32, F32, F32, F32, F32, _P, _P]
+    lib.nlosgr_fk_stolt.restype = ctypes.c_int
+    lib.nlosgr_fk_store.argtypes = [_P, I32, I32, I32, _P, _P]
+    lib.nlosgr_fk_store.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

@@ -12,7 +12,9 @@ image lacks: it raises.
 points from the capture's back-projection (nlosgr.backproject) instead of a carved set, so it does not depend
 on a first-bounce threshold and works on captures with a dark-count floor and shot noise.  It also takes a
 non-confocal capture (data_kwargs["laser_grid_positions"]: the laser spot differs from the sensed one), which
-the carving cannot; in such a file deltaT is the bin width in half-path units, as in a confocal one.
+the carving cannot; in such a file deltaT is the bin width in half-path units, as in a confocal one.  With
+method="fk" the volume drawn from is the capture's f-k migration (nlosgr.fk), a few passes over the capture in
+place of the full back-projection.
 """
 import numpy as np
 import torch
@@ -106,7 +108,8 @@ def sample_from_feasible_space_jittering(args, data_kwargs, margin=0.1, rho_scal
 
 @torch.no_grad()
 def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, device="cuda", start=None, end=None,
-                               power=0, filter="log", gamma=1.0, wavelength=None, cycles=4.0):
+                               power=0, filter="log", gamma=1.0, wavelength=None, cycles=4.0,
+                               method="backprojection", fk_power=4):
     """Data-driven initialisation that does not rest on a first-bounce threshold: init_gaussian_num voxels of
     the capture's back-projection (nlosgr.backproject.backproject_capture on a carving_volume_size^3 grid,
     clamped at 0) drawn with torch.multinomial in proportion to volume**gamma, with replacement, and jittered
@@ -114,8 +117,16 @@ def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, dev
     two.  Voxels outside the volume box shrunk by `margin` (the rule of init_rand_points) are not drawn.
     start / end default to args.start / args.end, or the whole capture.  wavelength: when given, the volume
     drawn from is the phasor-field magnitude (nlosgr.phasor.phasor_capture with this wavelength and `cycles`;
-    `filter` is then unused) instead of the filtered back-projection.  Returns (points [n,3], rho [n,1])."""
+    `filter` is then unused) instead of the filtered back-projection.  method="fk": the volume drawn from is the
+    capture's f-k migration cropped to the volume box (nlosgr.fk.fk_capture: a few passes over the capture instead
+    of a full back-projection; confocal captures with a lattice wall only; carving_volume_size, filter and
+    wavelength are unused), and the jitter is half that volume's own spacing per axis (wall spacing, bin width),
+    not the carving cube's; its falloff weight is fk_power (`power` belongs to the back-projection and the phasor
+    field).
+    Returns (points [n,3], rho [n,1])."""
     from .backproject import backproject_capture
+    if method not in ("backprojection", "fk"):
+        raise ValueError("nlosgr: method must be 'backprojection' or 'fk'")
     n = args.init_gaussian_num
     rho = np.random.rand(n, 1) * rho_scale
     if start is None:
@@ -124,12 +135,16 @@ def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, dev
         end = getattr(args, "end", None)
         if end is None:
             end = data_kwargs["nlos_data"].shape[0]
-    res = args.carving_volume_size
-    if wavelength is None:
-        out = backproject_capture(data_kwargs, res, start, end, power=power, filter=filter, positive=True)
+    if method == "fk":
+        from .fk import fk_capture
+        out = fk_capture(data_kwargs, start, end, power=fk_power)
     else:
-        from .phasor import phasor_capture
-        out = phasor_capture(data_kwargs, res, start, end, wavelength, cycles=cycles, power=power)
+        res = args.carving_volume_size
+        if wavelength is None:
+            out = backproject_capture(data_kwargs, res, start, end, power=power, filter=filter, positive=True)
+        else:
+            from .phasor import phasor_capture
+            out = phasor_capture(data_kwargs, res, start, end, wavelength, cycles=cycles, power=power)
     vol, grid = out["volume"], out["grid"]
     dev = vol.device
     pmin, pmax = data_kwargs["pmin"][:3].to(dev), data_kwargs["pmax"][:3].to(dev)
@@ -147,5 +162,8 @@ def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, dev
     idx = torch.multinomial(w / w.sum(), n, replacement=True)
     ny, nz = vol.shape[1], vol.shape[2]
     base = torch.stack((xs[idx // (ny * nz)], ys[(idx // nz) % ny], zs[idx % nz]), dim=1)
-    half = ((pmax - pmin) / (res - 1)) / 2.0
+    if method == "fk":
+        half = torch.stack([(t[-1] - t[0]) / max(t.numel() - 1, 1) for t in (xs, ys, zs)]) / 2.0
+    else:
+        half = ((pmax - pmin) / (res - 1)) / 2.0
     return base + (torch.rand_like(base) - 0.5) * 2 * half[None], rho
