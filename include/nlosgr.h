@@ -45,6 +45,8 @@
  *   nlosgr_sgld_noise   no counterpart (main.py:163-164, 215-217 leave it as future work): the position noise of
  *                          3DGS-MCMC's SGLD sampler after an optimizer step, from a counter-based generator
  *   nlosgr_fk_*         no counterpart: f-k migration of a confocal capture, the three passes around its two FFTs
+ *   nlosgr_rsd_*        no counterpart: fast phasor-field reconstruction (Rayleigh-Sommerfeld diffraction by FFT on the
+ *                          wall's lattice), the four passes around its FFTs; confocal or one laser spot
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -840,6 +842,80 @@ NLOSGR_API int nlosgr_fk_stolt(const float* spec /* [2H][2W][2nr][2] */, int32_t
                     void* hip_stream);
 NLOSGR_API int nlosgr_fk_store(const float* field /* [2H][2W][2nr][2] */, int32_t H, int32_t W, int32_t nr,
                     float* volume /* [W][nr][H] */, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Fast phasor-field reconstruction (an addition to ABI 13: four new symbols, nothing existing changes): the phasor
+ * field evaluated as Rayleigh-Sommerfeld diffraction, RSD (Liu, Bauer, Velten 2020).  No counterpart in the reference.
+ * For one depth plane and one temporal frequency the sum over the wall points is a 2-D convolution over the wall's
+ * lattice, so an FFT does it: O(N^3 log N) per band frequency against the O(N^5) of nlosgr_backproject_phasor.  It holds
+ * for a confocal capture and for one fixed laser spot with a scanned sensor lattice, because the weight of
+ * nlosgr_backproject_nc, (|x - laser| |x - wall|)^(power/2), separates into a laser factor and a sensor factor.  The
+ * FFTs are the caller's (the library links the HIP runtime alone); the four symbols are the passes around them.
+ *
+ * Input: rows [H W][nr] fp32; lattice point (m, n) is measured at (xs[n], y0, zs[m]) with uniform spacings sx, sz, and
+ * its row is rows[perm[m stride_m + n stride_n]], as for nlosgr_fk_load.  r0: radius of bin 0, dr: bin width, in
+ * half-path units.  ys [ny]: an ascending depth table of any spacing, D_j = ys[j] - y0 > 0.  wavelength, cycles: those
+ * of the Morlet wavelet of nlosgr/phasor.py (phasor_kernel).  power 0..4.  laser: one point, or none (confocal).  Nt:
+ * an even DFT length, nr <= Nt <= 8192.
+ *
+ * Band (built by the caller in double from the fp32 r0 and dr; nlosgr/rsd.py rsd_band):
+ *     P = wavelength / (2 dr), sigma_b = cycles P / 6, theta_q = 2 pi q / Nt, theta_0 = 2 pi / P,
+ *     q_0 = Nt / P, sigma_q = Nt / (2 pi sigma_b), q_lo = max(1, ceil(q_0 - 3 sigma_q)),
+ *     q_hi = min(Nt/2 - 1, floor(q_0 + 3 sigma_q)), nq = q_hi - q_lo + 1 (1..512),
+ *     coef[q] = exp(-(sigma_b (theta_q - theta_0))^2 / 2) exp(-i theta_q r0 / dr) / Nt, rounded to complex64.
+ *
+ * Stages (all work arrays complex64, interleaved re, im):
+ *   1          S = rfft(rows, n = Nt): [H W][Nt/2 + 1] (numpy's rfft: unnormalised, exp(-2 pi i ...)).
+ *   2 load     Pw[q - q_lo][m][n] = coef[q] S[row(m, n)][q] for m < H, n < W; zero elsewhere in [nq][2H][2W], written
+ *              in the same pass.
+ *   3          Pf = the 2-D DFT of every image of Pw (numpy's fft2), once.
+ *   then per chunk of depth planes j in [j0, j0 + nj):
+ *   5 kernel   K[j - j0][q - q_lo][a][b], a in [0, 2H), b in [0, 2W), with the signed offsets a' = a < H ? a : a - 2H
+ *              and b' likewise: K = 0 where a' = -H or b' = -W; otherwise
+ *                  d = sqrt((a' sz)^2 + (b' sx)^2 + D_j^2),  K = d^e exp(2 pi i frac(g q (d / dr) / Nt))
+ *              with (e, g) = (power, 1) without a laser and (power/2, 1/2) with one.
+ *   6          Kf = fft2(K).
+ *   7 apply    out[j][q] = Kf[j][q] Pf[q], broadcast over j; out may be Kf itself (in place), or disjoint from it.
+ *   8          o = ifft2(out), with the 1/(4 H W) normalisation.
+ *   9 gather   Phi[n][j][m] = sum_q L_q o[j - j0][q - q_lo][m][n] for m < H, n < W, q ascending, accumulated in fp32.
+ *              Without a laser L_q = 1; with one, dl = |(xs[n], ys[j], zs[m]) - laser| and
+ *              L_q = dl^(power/2) exp(2 pi i frac(q (dl / dr) / (2 Nt))); the factor dl^(power/2) multiplies the
+ *              finished sum once.  planes[0] = Re Phi and planes[1] = Im Phi in the voxel order [W][ny][H] of
+ *              nlosgr_voxel_grid, with the transpose nlosgr_fk_store does; mag (or NULL) as nlosgr_backproject_phasor
+ *              defines it: (float)sqrt((double)re*re + (double)im*im) of the fp32 planes.
+ *
+ * Meaning: Phi(x) = sum_p w(x, p) y_p((u(x, p) - r0) / dr), with u the half path (|x - laser| + |x - p|) / 2 (|x - p|
+ * for a confocal capture), w the weight of nlosgr_backproject / nlosgr_backproject_nc, and y_p row p filtered with the
+ * untruncated Morlet wavelet, band-limited to +-3 sigma_q, evaluated at the continuous bin coordinate and periodic in
+ * Nt.  Against nlosgr_backproject_phasor there is no linear interpolation between bins, no +-3 sigma truncation of the
+ * taps, and there is the period: Nt must be long enough that no pair's coordinate wraps onto the data (rsd_nt).
+ *
+ * Arithmetic: d, dl, d^e (one square root and products, rounded to fp32 once) and the turn count g q (d / dr) / Nt are
+ * formed in double; only the turn count's fraction goes to fp32 sincospif, as in nlosgr_fk_stolt (the phase reaches
+ * thousands of radians).  load and apply are single fp32 complex products.  No atomics; every output element is written
+ * by one lane from the inputs alone: bitwise repeatable.
+ * Validated on the host before any launch (NLOSGR_E_INVALID, text in the last-error string): H, W or ny outside 1..1024,
+ * depth planes leaving [0, ny), Nt odd or outside 2..8192, a band leaving [1, Nt/2 - 1] or of more than 512 frequencies,
+ * power outside 0..4, dr, sx or sz <= 0 or not finite, strides that leave [0, H W), a null or misaligned pointer (perm
+ * and mag may be NULL; the tables of gather only when there is no laser), a product that aliases the image spectrum or
+ * overlaps the kernel spectrum without being it.  r0 enters through coef alone, so r0 < 0 and a depth <= 0 are refused
+ * by the caller (nlosgr/rsd.py).  The library neither allocates nor synchronises.
+ * ------------------------------------------------------------------------------------- */
+NLOSGR_API int nlosgr_rsd_load(const float* spec /* [H W][Nt/2+1][2] */, const int32_t* perm /* [H W] or NULL */,
+                    const float* coef /* [nq][2] */, int32_t H, int32_t W, int32_t Nt, int32_t q_lo, int32_t nq,
+                    int32_t stride_m, int32_t stride_n, float* pw /* [nq][2H][2W][2] */, void* hip_stream);
+NLOSGR_API int nlosgr_rsd_kernel(const float* ys /* [ny] */, int32_t ny, int32_t j0, int32_t nj, float y0, int32_t H,
+                    int32_t W, float sx, float sz, float dr, int32_t Nt, int32_t q_lo, int32_t nq, int32_t power,
+                    int32_t laser /* 0: confocal */, float* K /* [nj][nq][2H][2W][2], 16-byte aligned */,
+                    void* hip_stream);
+NLOSGR_API int nlosgr_rsd_apply(const float* kf /* [nj][nq][2H][2W][2] */, const float* pf /* [nq][2H][2W][2] */,
+                    int32_t nj, int32_t nq, int32_t H, int32_t W, float* out /* kf, or disjoint from it */,
+                    void* hip_stream);
+NLOSGR_API int nlosgr_rsd_gather(const float* field /* [nj][nq][2H][2W][2] */, int32_t H, int32_t W, int32_t nq,
+                    int32_t q_lo, int32_t Nt, float dr, int32_t power, const float* xs /* [W] */,
+                    const float* ys /* [ny] */, const float* zs /* [H] */, int32_t ny, int32_t j0, int32_t nj,
+                    int32_t laser /* 0: confocal */, float lx, float ly, float lz,
+                    float* planes /* [2][W][ny][H] */, float* mag /* [W][ny][H] or NULL */, void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

@@ -17,6 +17,8 @@ Layers:
     nlosgr.backproject     the capture on a voxel grid: back-projection, time filters, backproject_capture
     nlosgr.phasor          phasor-field reconstruction: complex back-projection in one pass, phasor_capture
     nlosgr.fk              f-k migration of a confocal capture: three HIP passes around torch.fft, fk_capture
+    nlosgr.rsd             fast phasor field (Rayleigh-Sommerfeld diffraction by FFT on the wall's lattice): four HIP
+                           passes around torch.fft, rsd_capture; confocal or one laser spot
     nlosgr.forward_project its adjoint: voxel grid -> transients, voxel_transient, operator_norm, landweber
                            (both take lasers= for a non-confocal capture: the laser spot differs from the sensed one)
     nlosgr.irf             temporal instrument response: IRF, gaussian_irf, convolve_time (render -> capture)
@@ -31,11 +33,12 @@ __all__ = ["Geometry", "build_geometry", "relay_wall_grid", "volume_box_point", 
            "features_flat", "RenderConfig", "RenderFn", "render", "render_forward", "render_backward", "bboxes",
            "Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply",
            "backproject_capture", "time_filter", "phasor_capture", "phasor_kernel",
-           "fk_capture", "fk_migrate"]
+           "fk_capture", "fk_migrate", "rsd_capture", "rsd_reconstruct"]
 
 _BP_NAMES = ("backproject_capture", "time_filter")
 _PH_NAMES = ("phasor_capture", "phasor_kernel")
 _FK_NAMES = ("fk_capture", "fk_migrate")
+_RSD_NAMES = ("rsd_capture", "rsd_reconstruct")
 _MESH_NAMES = ("Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply")
 
 
@@ -55,4 +58,7 @@ def __getattr__(name):
     if name in _FK_NAMES:
         from . import fk
         return getattr(fk, name)
+    if name in _RSD_NAMES:
+        from . import rsd
+        return getattr(rsd, name)
     raise AttributeError(f"module 'nlosgr' has no attribute {name!r}")

@@ -120,7 +120,8 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_forward_project_workspace_bytes", "nlosgr_forward_project",
            "nlosgr_backproject_nc", "nlosgr_forward_project_nc_workspace_bytes", "nlosgr_forward_project_nc",
            "nlosgr_backproject_phasor", "nlosgr_render_nc_workspace_bytes", "nlosgr_render_nc_fwd", "nlosgr_render_nc_bwd",
-           "nlosgr_sgld_noise", "nlosgr_fk_load", "nlosgr_fk_stolt", "nlosgr_fk_store", "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
+           "nlosgr_sgld_noise", "nlosgr_fk_load", "nlosgr_fk_stolt", "nlosgr_fk_store",
+           "nlosgr_rsd_load", "nlosgr_rsd_kernel", "nlosgr_rsd_apply", "nlosgr_rsd_gather", "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
 _load_error = None
@@ -233,6 +234,15 @@ def load():
     lib.nlosgr_fk_stolt.restype = ctypes.c_int
     lib.nlosgr_fk_store.argtypes = [_P, I32, I32, I32, _P, _P]
     lib.nlosgr_fk_store.restype = ctypes.c_int
+    lib.nlosgr_rsd_load.argtypes = [_P, _P, _P, I32, I32, I32, I32, I32, I32, I32, _P, _P]
+    lib.nlosgr_rsd_load.restype = ctypes.c_int
+    lib.nlosgr_rsd_kernel.argtypes = [_P, I32, I32, I32, F32, I32, I32, F32, F32, F32, I32, I32, I32, I32, I32, _P, _P]
+    lib.nlosgr_rsd_kernel.restype = ctypes.c_int
+    lib.nlosgr_rsd_apply.argtypes = [_P, _P, I32, I32, I32, I32, _P, _P]
+    lib.nlosgr_rsd_apply.restype = ctypes.c_int
+    lib.nlosgr_rsd_gather.argtypes = [_P, I32, I32, I32, I32, I32, F32, I32, _P, _P, _P, I32, I32, I32, I32, F32, F32,
+                                      F32, _P, _P, _P]
+    lib.nlosgr_rsd_gather.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

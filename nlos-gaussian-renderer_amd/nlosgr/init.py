@@ -122,11 +122,16 @@ def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, dev
     of a full back-projection; confocal captures with a lattice wall only; carving_volume_size, filter and
     wavelength are unused), and the jitter is half that volume's own spacing per axis (wall spacing, bin width),
     not the carving cube's; its falloff weight is fk_power (`power` belongs to the back-projection and the phasor
-    field).
+    field).  method="rsd": the volume drawn from is the fast phasor field (nlosgr.rsd.rsd_capture with `wavelength`,
+    which it needs, `cycles` and `power`: the wall's lattice x carving_volume_size depth planes, cropped to the
+    volume box; a confocal capture or one laser spot, on a lattice wall), and the jitter is again half that
+    volume's own spacing per axis.
     Returns (points [n,3], rho [n,1])."""
     from .backproject import backproject_capture
-    if method not in ("backprojection", "fk"):
-        raise ValueError("nlosgr: method must be 'backprojection' or 'fk'")
+    if method not in ("backprojection", "fk", "rsd"):
+        raise ValueError("nlosgr: method must be 'backprojection', 'fk' or 'rsd'")
+    if method == "rsd" and wavelength is None:
+        raise ValueError("nlosgr: method='rsd' is the phasor field: it needs wavelength=")
     n = args.init_gaussian_num
     rho = np.random.rand(n, 1) * rho_scale
     if start is None:
@@ -138,6 +143,9 @@ def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, dev
     if method == "fk":
         from .fk import fk_capture
         out = fk_capture(data_kwargs, start, end, power=fk_power)
+    elif method == "rsd":
+        from .rsd import rsd_capture
+        out = rsd_capture(data_kwargs, args.carving_volume_size, start, end, wavelength, cycles=cycles, power=power)
     else:
         res = args.carving_volume_size
         if wavelength is None:
@@ -162,7 +170,7 @@ def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, dev
     idx = torch.multinomial(w / w.sum(), n, replacement=True)
     ny, nz = vol.shape[1], vol.shape[2]
     base = torch.stack((xs[idx // (ny * nz)], ys[(idx // nz) % ny], zs[idx % nz]), dim=1)
-    if method == "fk":
+    if method in ("fk", "rsd"):
         half = torch.stack([(t[-1] - t[0]) / max(t.numel() - 1, 1) for t in (xs, ys, zs)]) / 2.0
     else:
         half = ((pmax - pmin) / (res - 1)) / 2.0
