@@ -47,6 +47,8 @@
  *   nlosgr_fk_*         no counterpart: f-k migration of a confocal capture, the three passes around its two FFTs
  *   nlosgr_rsd_*        no counterpart: fast phasor-field reconstruction (Rayleigh-Sommerfeld diffraction by FFT on the
  *                          wall's lattice), the four passes around its FFTs; confocal or one laser spot
+ *   nlosgr_lct_*        no counterpart: the light-cone transform of a confocal capture (Wiener-filtered inversion of the
+ *                          confocal measurement operator), the four passes around its FFTs
  */
 #ifndef NLOSGR_H
 #define NLOSGR_H
@@ -916,6 +918,71 @@ NLOSGR_API int nlosgr_rsd_gather(const float* field /* [nj][nq][2H][2W][2] */, i
                     const float* ys /* [ny] */, const float* zs /* [H] */, int32_t ny, int32_t j0, int32_t nj,
                     int32_t laser /* 0: confocal */, float lx, float ly, float lz,
                     float* planes /* [2][W][ny][H] */, float* mag /* [W][ny][H] or NULL */, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Light-cone transform, LCT (an addition to ABI 13: four new symbols, nothing existing changes): O'Toole, Lindell,
+ * Wetzstein 2018.  No counterpart in the reference.  The project's own discretisation, not a port of the published
+ * code.  A confocal row obeys
+ *     r^3 tau(x', z', r) = integral rho(x, z, sqrt(u)) / (2 sqrt(u)) delta(rho_lat^2 + u - v) dx dz du,   v = r^2,
+ * with r the half path: in (x, z, v) a 3-D convolution with a paraboloid, inverted here by a Wiener filter.  It is
+ * shift-invariant in v, so a window that starts at any bin needs no special handling.  The FFTs are the caller's (the
+ * library links the HIP runtime alone); the four symbols are the passes around them.
+ *
+ * Input: rows [H W][nr], the lattice, perm, the strides, r0, dr and power as for nlosgr_fk_load; nv: the number of
+ * depth-squared cells, 1..2048.  Nz = 2 H, Nx = 2 W, Nv = 2 nv; the work arrays are complex64 [Nz][Nx][Nv],
+ * interleaved (re, im).
+ *
+ * Edges (formed by the caller in double from the fp32 r0 and dr; nlosgr/lct.py lct_resampling): bin j owns
+ * r in [e_j, e_j+1), e_j = r0 + (j - 1/2) dr with e_0 clamped at 0;  v_lo = e_0^2, v_hi = e_nr^2, dv = (v_hi - v_lo) / nv;
+ * cell i owns r in [t_i, t_i+1), t_i = sqrt(v_lo + i dv), with t_0 = e_0 and t_nv = e_nr exactly.
+ *
+ * Resampling operator R [nv][nr]:
+ *     R[i][j] = |cell i n bin j| / (t_i+1 - t_i) / ((t_i + t_i+1) / 2),
+ * the share of cell i inside bin j over the cell's mean radius (the closed form of (1/dv) integral dv / sqrt(v) over the
+ * overlap).  Every row and every column holds one contiguous run of non-zeros, nnz <= nv + nr.  It is passed as run
+ * tables, rounded to fp32 from double: row i holds weight[start[i] .. start[i+1]) at the bins first[i], first[i] + 1, ...
+ * (first [nv], start [nv + 1], weight [nnz]); R^T likewise, per bin j its run of cells (first [nr], start [nr + 1]).
+ * The kernels clamp every table entry before use: a bad table reads a wrong bin, never outside an array.
+ *
+ * Stages:
+ *   1 load    psi[v][j] = max(rows[v][j], 0) (r0 + j dr)^power in fp32, the arithmetic of nlosgr_fk_load without
+ *             `amplitude`;  g[m][n][i] = sum_j R[i][j] psi[v][j], j ascending, acc = fma(weight, psi, acc) in fp32.
+ *             pad = (g, 0) at [0:H][0:W][0:nv] of a zero array; the padding is zero-filled in the same pass.
+ *   2 kernel  with signed DFT indices c (z), b (x):  s = ((b sx)^2 + (c sz)^2) / dv in fp64, k = floor(s), f = s - k;
+ *                 K[c][b][k] = scale (1 - f) where k <= nv - 1,  K[c][b][k+1] = scale f where k + 1 <= nv - 1,
+ *             zero everywhere else (no anticausal half, nothing at or beyond nv), every element written.  scale =
+ *             1 / ||K||_2 is the caller's, in double from the same formula over the 2H x 2W columns.
+ *   3         Fk = fftn(K), S = fftn(pad) (numpy's fftn: unnormalised, exp(-2 pi i ...)).
+ *   4 filter  G = conj(Fk) / (|Fk|^2 + 1 / snr) (mode 0, Wiener), G = conj(Fk) (mode 1, back-projection), or G = the
+ *             array itself (mode 2: an inverse built by an earlier call).  spec NULL: out = G (modes 0, 1); otherwise
+ *             out = spec G, elementwise.  out may be kf or spec (in place).  G depends on the lattice and the window
+ *             alone, so it can be kept for the next capture; both routes give the same bits.
+ *   5         o = ifftn(out), with the 1/N normalisation.
+ *   6 store   volume[n][j][m] = max(sum_i R[i][j] Re o[m][n][i], 0), i ascending, acc = fma(weight, Re o, acc) in fp32:
+ *             [nx = W][ny = nr][nz = H] in the voxel order of nlosgr_voxel_grid; voxel (n, j, m) is the point
+ *             (xs[n], y0 + r0 + j dr, zs[m]), as for nlosgr_fk_store.
+ * No atomics; every output element is written by one lane in a fixed summation order: bitwise repeatable.
+ * Arithmetic: csrc/nlosgr_lct.hip.
+ * Validated on the host before any launch (NLOSGR_E_INVALID, text in the last-error string): H, W or nr outside
+ * 1..1024, nv outside 1..2048, power outside 0..4, dr <= 0 or not finite, r0 < 0 or not finite, sx, sz, dv, scale or
+ * snr <= 0 or not finite, a mode outside 0..2, strides that leave [0, H W), nnz outside 1..nv + nr, a null or misaligned
+ * pointer (perm may be NULL; spec in modes 0 and 1), a volume that aliases the field.  The library neither allocates
+ * nor synchronises.
+ * ------------------------------------------------------------------------------------- */
+NLOSGR_API int nlosgr_lct_load(const float* rows /* [H W][nr] */, const int32_t* perm /* [H W] or NULL */, int32_t H,
+                    int32_t W, int32_t nr, int32_t nv, int32_t stride_m, int32_t stride_n, float r0, float dr,
+                    int32_t power, const int32_t* first /* [nv] */, const int32_t* start /* [nv + 1] */,
+                    const float* weight /* [nnz] */, int32_t nnz,
+                    float* pad /* [2H][2W][2nv][2], 16-byte aligned */, void* hip_stream);
+NLOSGR_API int nlosgr_lct_kernel(int32_t H, int32_t W, int32_t nv, float sx, float sz, double dv, double scale,
+                    float* K /* [2H][2W][2nv][2], 16-byte aligned */, void* hip_stream);
+NLOSGR_API int nlosgr_lct_filter(const float* kf /* [2H][2W][2nv][2]: Fk, or G in mode 2 */,
+                    const float* spec /* the same shape, or NULL */, int32_t H, int32_t W, int32_t nv, float snr,
+                    int32_t mode, float* out /* the same shape; all three 16-byte aligned */, void* hip_stream);
+NLOSGR_API int nlosgr_lct_store(const float* field /* [2H][2W][2nv][2] */, int32_t H, int32_t W, int32_t nr,
+                    int32_t nv, const int32_t* first /* [nr]: the tables of R^T */,
+                    const int32_t* start /* [nr + 1] */, const float* weight /* [nnz] */, int32_t nnz,
+                    float* volume /* [W][nr][H] */, void* hip_stream);
 
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);

@@ -26,6 +26,7 @@
 // row: lanes run along time for the 8-byte reads and along z for the writes (16, 8 or 4 bytes per lane as H
 // divides by 4, 2 or not).
 #include "nlosgr_common.hpp"
+#include "nlosgr_fk.hpp"
 
 using namespace nlosgr;
 using namespace nlosgr::detail;
@@ -42,16 +43,6 @@ struct FkLoadArgs {
     float r0, dr;
     float4* pad;           // [Nz * Nx][nr]: two complex bins each
 };
-
-template <int POWER, bool AMP>
-__device__ __forceinline__ float fk_psi(float h, int j, float r0, float dr) {
-#pragma clang fp contract(off)
-    const float r = fmaf((float)j, dr, r0);
-    const float r2 = r * r;
-    const float w = POWER == 0 ? 1.0f : (POWER == 1 ? r : (POWER == 2 ? r2 : (POWER == 3 ? r2 * r : r2 * r2)));
-    const float v = fmaxf(h, 0.0f) * w;
-    return AMP ? fsqrt(v) : v;
-}
 
 // VEC2: rows are 8-byte aligned and nr is even, so a lane's two bins come from one 8-byte read
 template <int POWER, bool AMP, bool VEC2>

@@ -19,6 +19,8 @@ Layers:
     nlosgr.fk              f-k migration of a confocal capture: three HIP passes around torch.fft, fk_capture
     nlosgr.rsd             fast phasor field (Rayleigh-Sommerfeld diffraction by FFT on the wall's lattice): four HIP
                            passes around torch.fft, rsd_capture; confocal or one laser spot
+    nlosgr.lct             light-cone transform of a confocal capture (Wiener-filtered inversion): four HIP passes
+                           around torch.fft, lct_capture
     nlosgr.forward_project its adjoint: voxel grid -> transients, voxel_transient, operator_norm, landweber
                            (both take lasers= for a non-confocal capture: the laser spot differs from the sensed one)
     nlosgr.irf             temporal instrument response: IRF, gaussian_irf, convolve_time (render -> capture)
@@ -33,12 +35,13 @@ __all__ = ["Geometry", "build_geometry", "relay_wall_grid", "volume_box_point", 
            "features_flat", "RenderConfig", "RenderFn", "render", "render_forward", "render_backward", "bboxes",
            "Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply",
            "backproject_capture", "time_filter", "phasor_capture", "phasor_kernel",
-           "fk_capture", "fk_migrate", "rsd_capture", "rsd_reconstruct"]
+           "fk_capture", "fk_migrate", "rsd_capture", "rsd_reconstruct", "lct_capture", "lct_reconstruct"]
 
 _BP_NAMES = ("backproject_capture", "time_filter")
 _PH_NAMES = ("phasor_capture", "phasor_kernel")
 _FK_NAMES = ("fk_capture", "fk_migrate")
 _RSD_NAMES = ("rsd_capture", "rsd_reconstruct")
+_LCT_NAMES = ("lct_capture", "lct_reconstruct")
 _MESH_NAMES = ("Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply")
 
 
@@ -61,4 +64,7 @@ def __getattr__(name):
     if name in _RSD_NAMES:
         from . import rsd
         return getattr(rsd, name)
+    if name in _LCT_NAMES:
+        from . import lct
+        return getattr(lct, name)
     raise AttributeError(f"module 'nlosgr' has no attribute {name!r}")

@@ -121,7 +121,8 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_backproject_nc", "nlosgr_forward_project_nc_workspace_bytes", "nlosgr_forward_project_nc",
            "nlosgr_backproject_phasor", "nlosgr_render_nc_workspace_bytes", "nlosgr_render_nc_fwd", "nlosgr_render_nc_bwd",
            "nlosgr_sgld_noise", "nlosgr_fk_load", "nlosgr_fk_stolt", "nlosgr_fk_store",
-           "nlosgr_rsd_load", "nlosgr_rsd_kernel", "nlosgr_rsd_apply", "nlosgr_rsd_gather", "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
+           "nlosgr_rsd_load", "nlosgr_rsd_kernel", "nlosgr_rsd_apply", "nlosgr_rsd_gather",
+           "nlosgr_lct_load", "nlosgr_lct_kernel", "nlosgr_lct_filter", "nlosgr_lct_store", "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
 _load_error = None
@@ -243,6 +244,15 @@ def load():
     lib.nlosgr_rsd_gather.argtypes = [_P, I32, I32, I32, I32, I32, F32, I32, _P, _P, _P, I32, I32, I32, I32, F32, F32,
                                       F32, _P, _P, _P]
     lib.nlosgr_rsd_gather.restype = ctypes.c_int
+    F64 = ctypes.c_double
+    lib.nlosgr_lct_load.argtypes = [_P, _P, I32, I32, I32, I32, I32, I32, F32, F32, I32, _P, _P, _P, I32, _P, _P]
+    lib.nlosgr_lct_load.restype = ctypes.c_int
+    lib.nlosgr_lct_kernel.argtypes = [I32, I32, I32, F32, F32, F64, F64, _P, _P]
+    lib.nlosgr_lct_kernel.restype = ctypes.c_int
+    lib.nlosgr_lct_filter.argtypes = [_P, _P, I32, I32, I32, F32, I32, _P, _P]
+    lib.nlosgr_lct_filter.restype = ctypes.c_int
+    lib.nlosgr_lct_store.argtypes = [_P, I32, I32, I32, I32, _P, _P, _P, I32, _P, _P]
+    lib.nlosgr_lct_store.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

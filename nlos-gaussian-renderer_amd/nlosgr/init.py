@@ -14,7 +14,8 @@ on a first-bounce threshold and works on captures with a dark-count floor and sh
 non-confocal capture (data_kwargs["laser_grid_positions"]: the laser spot differs from the sensed one), which
 the carving cannot; in such a file deltaT is the bin width in half-path units, as in a confocal one.  With
 method="fk" the volume drawn from is the capture's f-k migration (nlosgr.fk), a few passes over the capture in
-place of the full back-projection.
+place of the full back-projection.  `sample_from_volume` is its drawing half alone, for a volume that is already
+there (the "volume" and "grid" of nlosgr.lct.lct_capture or of any other *_capture).
 """
 import numpy as np
 import torch
@@ -174,4 +175,38 @@ def sample_from_backprojection(args, data_kwargs, margin=0.1, rho_scale=0.1, dev
         half = torch.stack([(t[-1] - t[0]) / max(t.numel() - 1, 1) for t in (xs, ys, zs)]) / 2.0
     else:
         half = ((pmax - pmin) / (res - 1)) / 2.0
+    return base + (torch.rand_like(base) - 0.5) * 2 * half[None], rho
+
+
+@torch.no_grad()
+def sample_from_volume(args, data_kwargs, volume, grid, margin=0.1, rho_scale=0.1, gamma=1.0):
+    """The drawing half of sample_from_backprojection for a volume that is already there: init_gaussian_num voxels
+    of `volume` [nx, ny, nz] on `grid` (a voxelize.VoxelGrid) drawn with torch.multinomial in proportion to
+    max(volume, 0)**gamma, with replacement, and jittered by up to half the grid's own spacing per axis
+    ((last - first) / (n - 1) of each table); rho ~ U(0, rho_scale) (numpy).  Voxels outside the volume box shrunk
+    by `margin` are not drawn.  It takes the "volume" and "grid" of any *_capture result:
+        out = lct_capture(dk, start, end);  sample_from_volume(args, dk, **{k: out[k] for k in ("volume", "grid")})
+    The generators are called as sample_from_backprojection calls them: numpy for rho first, then torch.multinomial
+    and torch.rand_like on the volume's device.  Returns (points [n,3], rho [n,1])."""
+    n = args.init_gaussian_num
+    rho = np.random.rand(n, 1) * rho_scale
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 3 or tuple(volume.shape) != tuple(grid.shape):
+        raise ValueError(f"nlosgr: volume must be a tensor of the grid's shape {tuple(grid.shape)}")
+    vol = volume.detach()
+    dev = vol.device
+    pmin, pmax = data_kwargs["pmin"][:3].to(dev), data_kwargs["pmax"][:3].to(dev)
+    lo = pmin + (pmin * margin).abs()
+    hi = pmax - (pmax * margin).abs()
+    xs, ys, zs = grid.on(dev)
+    inside = (((xs >= lo[0]) & (xs <= hi[0]))[:, None, None] & ((ys >= lo[1]) & (ys <= hi[1]))[None, :, None]
+              & ((zs >= lo[2]) & (zs <= hi[2]))[None, None, :])
+    w = torch.where(inside, vol, torch.zeros_like(vol)).clamp_min(0).reshape(-1).double()
+    if gamma != 1.0:
+        w = w ** gamma
+    if not bool(torch.isfinite(w).all()) or not float(w.sum()) > 0:
+        raise RuntimeError("nlosgr: the volume is zero (or not finite) inside the margin box: nothing to sample from")
+    idx = torch.multinomial(w / w.sum(), n, replacement=True)
+    ny, nz = vol.shape[1], vol.shape[2]
+    base = torch.stack((xs[idx // (ny * nz)], ys[(idx // nz) % ny], zs[idx % nz]), dim=1)
+    half = torch.stack([(t[-1] - t[0]) / max(t.numel() - 1, 1) for t in (xs, ys, zs)]) / 2.0
     return base + (torch.rand_like(base) - 0.5) * 2 * half[None], rho
