@@ -984,6 +984,58 @@ NLOSGR_API int nlosgr_lct_store(const float* field /* [2H][2W][2nv][2] */, int32
                     const int32_t* start /* [nr + 1] */, const float* weight /* [nnz] */, int32_t nnz,
                     float* volume /* [W][nr][H] */, void* hip_stream);
 
+/* ---------------------------------------------------------------------------------------
+ * LCT operator pair (an addition to ABI 13: four new symbols, nothing existing changes).  The confocal measurement
+ * operator on the lattice and its exact adjoint, built from the parts of the light-cone transform above: R, K and
+ * Fk = fftn(K) are the same, T is the [W, nr, H] <-> [H, W, nr] transpose, and nothing is clamped, so both take a
+ * residual.
+ *
+ *     w_j  = (r0 + j dr)^power, power in -4..4: r = fma(j, dr, r0) in fp32, the power by the multiplications of
+ *            nlosgr_fk_load, a negative power as one IEEE division 1 / r^|power|, and 0 where r <= 0.
+ *     A    : volume [W][nr][H] -> rows [H W][nr]
+ *            g[m][n][i]       = sum_j R[i][j] volume[n][j][m]                        nlosgr_lct_load_volume
+ *            o                = Re ifftn( fftn(pad g) Fk )                           nlosgr_lct_filter, mode 2, kf = Fk
+ *            rows[v(m,n)][j]  = w_j sum_i R[i][j] o[m][n][i]                         nlosgr_lct_store_rows
+ *     A^T  : rows -> volume
+ *            g[m][n][i]       = sum_j R[i][j] (w_j rows[v][j])                       nlosgr_lct_load_rows
+ *            o                = Re ifftn( fftn(pad g) conj(Fk) )                     nlosgr_lct_filter, mode 1
+ *            volume[n][j][m]  = sum_i R[i][j] o[m][n][i]                             nlosgr_lct_store_volume
+ *
+ * v(m, n) = perm[m stride_m + n stride_n] as in nlosgr_lct_load.  <A v, h> = <v, A^T h> holds for the float64
+ * restatement to rounding.  With power = -3, A is the physical confocal transient of forward_project at power -4 up to
+ * the factor dv / (2 dr scale) per unit voxel value (scale: nlosgr_lct_kernel's; R carries one 1 / r).
+ *
+ *   load_volume   j ascending, acc = fma(weight, volume, acc) in fp32; every element of pad is written, the zeros for
+ *                 m >= H, n >= W and i >= nv included.  first/start/weight: the tables of R.
+ *   store_rows    i ascending, acc = fma(weight, Re field, acc), then one multiply by w_j; signed.  Reads the
+ *                 [0:H][0:W][0:nv] corner of field only.  Rows that no lattice point names are left untouched.
+ *                 first/start/weight: the tables of R^T.
+ *   load_rows     nlosgr_lct_load with psi = rows[v][j] w_j, no clamp, power -4..4.  For power 0..4 and rows >= 0 the
+ *                 bits of nlosgr_lct_load.
+ *   store_volume  nlosgr_lct_store without the clamp.  Where the sum is >= 0 the bits of nlosgr_lct_store.
+ * No atomics, one writer per element in a fixed order: bitwise repeatable.  Table entries are clamped as above.
+ * Validated on the host before any launch as the four passes above, with power in -4..4 for load_rows and store_rows;
+ * pad and field must be 8-byte aligned (16 for load_rows), and no output may alias its input.
+ * ------------------------------------------------------------------------------------- */
+NLOSGR_API int nlosgr_lct_load_volume(const float* volume /* [W][nr][H] */, int32_t H, int32_t W, int32_t nr,
+                    int32_t nv, const int32_t* first /* [nv] */, const int32_t* start /* [nv + 1] */,
+                    const float* weight /* [nnz] */, int32_t nnz, float* pad /* [2H][2W][2nv][2] */,
+                    void* hip_stream);
+NLOSGR_API int nlosgr_lct_store_rows(const float* field /* [2H][2W][2nv][2] */, const int32_t* perm /* [H W] or NULL */,
+                    int32_t H, int32_t W, int32_t nr, int32_t nv, int32_t stride_m, int32_t stride_n, float r0,
+                    float dr, int32_t power, const int32_t* first /* [nr]: the tables of R^T */,
+                    const int32_t* start /* [nr + 1] */, const float* weight /* [nnz] */, int32_t nnz,
+                    float* rows /* [H W][nr] */, void* hip_stream);
+NLOSGR_API int nlosgr_lct_load_rows(const float* rows /* [H W][nr] */, const int32_t* perm /* [H W] or NULL */,
+                    int32_t H, int32_t W, int32_t nr, int32_t nv, int32_t stride_m, int32_t stride_n, float r0,
+                    float dr, int32_t power, const int32_t* first /* [nv] */, const int32_t* start /* [nv + 1] */,
+                    const float* weight /* [nnz] */, int32_t nnz,
+                    float* pad /* [2H][2W][2nv][2], 16-byte aligned */, void* hip_stream);
+NLOSGR_API int nlosgr_lct_store_volume(const float* field /* [2H][2W][2nv][2] */, int32_t H, int32_t W, int32_t nr,
+                    int32_t nv, const int32_t* first /* [nr]: the tables of R^T */,
+                    const int32_t* start /* [nr + 1] */, const float* weight /* [nnz] */, int32_t nnz,
+                    float* volume /* [W][nr][H] */, void* hip_stream);
+
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);
 

@@ -21,6 +21,17 @@
 //                      G formed on the fly are the same fp32 values, so both routes give the same bits.
 //   nlosgr_lct_store   volume[n][j][m] = max(sum_i R[i][j] Re o[m][n][i], 0), i ascending, acc = fmaf(w, o, acc).
 //
+// The operator pair (A: volume -> rows, A^T: rows -> volume; include/nlosgr.h) adds the passes that run the same two
+// resamplings the other way round and the signed variants of load and store.  w_j = (r0 + j dr)^power, power -4..4:
+// r = fmaf(j, dr, r0), |power| by the multiplications of fk_psi, a negative power as one IEEE division 1 / r^|power|,
+// and 0 where r <= 0.
+//
+//   nlosgr_lct_load_volume   pad[m][n][i] = (sum_j R[i][j] volume[n][j][m], 0), j ascending, acc = fmaf(w, v, acc);
+//                            zero for m >= H, n >= W or i >= nv.  No clamp, no weight.
+//   nlosgr_lct_store_rows    rows[v][j] = w_j sum_i R[i][j] Re o[m][n][i], i ascending, fmaf, one multiply at the end.
+//   nlosgr_lct_load_rows     nlosgr_lct_load with psi = rows[v][j] w_j (no clamp): the same kernel, another instance.
+//   nlosgr_lct_store_volume  nlosgr_lct_store without the clamp: the same kernel, another instance.
+//
 // Shape.  load, kernel and filter give a workgroup one (c, b) column; a lane writes two adjacent complex cells (16
 // bytes), the zeros included, so none needs a memset.  load stages the weighted row in LDS (nr <= 1024 floats) and a
 // lane gathers its two cells' short runs from it.  store owns a tile of 64 bins x 64 z of one wall column: the
@@ -29,6 +40,15 @@
 // its bin, so the run tables are wave-uniform and the LDS reads of a wave hit 64 different banks), and write along z
 // coalesced.  No atomics; every output element is written by one lane in a fixed order: bitwise repeatable.  Table
 // entries are clamped before use: a bad table reads a wrong bin or cell, never outside an array.
+//
+// load_volume mirrors store: a workgroup owns 64 cells x 64 z of one wall column.  The tile's bins form one
+// contiguous range, read in chunks of 64 bins with lanes along z (the volume's fastest axis, coalesced) into an LDS
+// tile [bin][z] padded to 65 floats a row; then lanes run along the cells, each summing its own run for the 16 z of
+// its wave (a wave reads addresses bin 65 + z with z wave-uniform: neighbouring cells share a bin, a broadcast, or
+// sit in neighbouring bins, distinct banks), and write 8-byte complex cells along i, coalesced.  The same workgroup
+// writes the tile's seven zero images in the padding (m + H, n + W, i + nv), so every element of pad has one writer.
+// store_rows needs no transpose: a workgroup stages the nv real parts of one lattice column in LDS and lanes run
+// along j.
 #include "nlosgr_common.hpp"
 #include "nlosgr_fk.hpp"
 
@@ -63,8 +83,23 @@ struct LctLoadArgs {
     const float* weight;   // [nnz]
     int H, W, nr, nv, nnz, sm, sn;
     float r0, dr;
+    int power;             // read by the signed instance alone
     float4* pad;           // [Nz * Nx][nv]: two complex cells each
 };
+
+constexpr int kLctSigned = -1;  // lct_load_kernel<kLctSigned>: no clamp, the power (-4..4) from the arguments
+
+// (r0 + j dr)^power, power in -4..4: fk_psi's r and its multiplications; 1 / r^|power| by one IEEE division, 0 where
+// r <= 0
+__device__ __forceinline__ float lct_weight(int power, int j, float r0, float dr) {
+#pragma clang fp contract(off)
+    const float r = fmaf((float)j, dr, r0);
+    const float r2 = r * r;
+    const int p = power < 0 ? -power : power;
+    const float w = p == 0 ? 1.0f : (p == 1 ? r : (p == 2 ? r2 : (p == 3 ? r2 * r : r2 * r2)));
+    if (power >= 0) return w;
+    return r > 0.0f ? 1.0f / w : 0.0f;
+}
 
 __device__ __forceinline__ float lct_cell(const LctLoadArgs& a, const float* psi, int i) {
     const LctRun r = lct_run(a.first, a.start, i, a.nr, a.nnz);
@@ -85,7 +120,10 @@ __global__ __launch_bounds__(kBlock) void lct_load_kernel(LctLoadArgs a) {
         if (a.perm) v = a.perm[v];
         v = min(max(v, 0), a.H * a.W - 1);                  // a bad perm entry reads a wrong row, never outside the rows
         const float* const row = a.rows + (size_t)v * a.nr;
-        for (int j = threadIdx.x; j < a.nr; j += kBlock) psi[j] = fk_psi<POWER, false>(row[j], j, a.r0, a.dr);
+        for (int j = threadIdx.x; j < a.nr; j += kBlock) {
+            if constexpr (POWER == kLctSigned) psi[j] = row[j] * lct_weight(a.power, j, a.r0, a.dr);
+            else psi[j] = fk_psi<POWER, false>(row[j], j, a.r0, a.dr);
+        }
         __syncthreads();
     }
     for (int p = threadIdx.x; p < a.nv; p += kBlock) {
@@ -183,6 +221,7 @@ struct LctStoreArgs {
 };
 
 // block (jt, mt, n): the tile j in [64 jt, +64), m in [64 mt, +64) of wall column n
+template <bool CLAMP>
 __global__ __launch_bounds__(kBlock) void lct_store_kernel(LctStoreArgs a) {
     __shared__ float cells[kLctTile][kLctTile + 1];         // [z][cell of the chunk]
     __shared__ int run_f[kLctTile], run_s[kLctTile], run_n[kLctTile];
@@ -228,8 +267,104 @@ __global__ __launch_bounds__(kBlock) void lct_store_kernel(LctStoreArgs a) {
 #pragma unroll
         for (int q = 0; q < kLctBinsPerLane; ++q) {
             const int j = j0 + wave + q * kWaves;
-            if (j < a.nr) a.vol[((size_t)n * a.nr + j) * a.H + m] = fmaxf(acc[q], 0.0f);
+            if (j < a.nr) a.vol[((size_t)n * a.nr + j) * a.H + m] = CLAMP ? fmaxf(acc[q], 0.0f) : acc[q];
         }
+    }
+}
+
+struct LctLoadVolumeArgs {
+    const float* vol;      // [W][nr][H]
+    const int* first;      // [nv]: the tables of R
+    const int* start;      // [nv + 1]
+    const float* weight;   // [nnz]
+    float2* pad;           // [Nz][Nx][Nv]
+    int H, W, nr, nv, nnz;
+};
+
+// block (it, mt, n): the tile i in [64 it, +64), m in [64 mt, +64) of wall column n, and its seven zero images
+__global__ __launch_bounds__(kBlock) void lct_load_volume_kernel(LctLoadVolumeArgs a) {
+    __shared__ float bins[kLctTile][kLctTile + 1];          // [bin of the chunk][z]
+    __shared__ int run_f[kLctTile], run_s[kLctTile], run_n[kLctTile];
+    const int t = threadIdx.x;
+    const int i0 = blockIdx.x * kLctTile, m0 = blockIdx.y * kLctTile, n = blockIdx.z;
+    const size_t Nx = 2 * (size_t)a.W, Nv = 2 * (size_t)a.nv;
+    if (t < kLctTile) {
+        LctRun r = {0, 0, 0};
+        if (i0 + t < a.nv) r = lct_run(a.first, a.start, i0 + t, a.nr, a.nnz);
+        run_f[t] = r.f; run_s[t] = r.s; run_n[t] = r.cnt;
+    }
+    __syncthreads();
+    int jbeg = a.nr, jend = 0;                              // the tile's bins: [jbeg, jend), inside [0, nr)
+    for (int q = 0; q < kLctTile; ++q)
+        if (run_n[q] > 0) {
+            jbeg = min(jbeg, run_f[q]);
+            jend = max(jend, run_f[q] + run_n[q]);
+        }
+    const int lane = t & 63, wave = t >> 6;
+    const int f = run_f[lane], cnt = run_n[lane];           // this lane's cell
+    const float* const w = a.weight + run_s[lane];
+    const int zn = min(kLctTile, a.H - m0);                 // the tile's z: [0, zn)
+    float acc[kLctBinsPerLane];                             // z = wave + q kWaves
+#pragma unroll
+    for (int q = 0; q < kLctBinsPerLane; ++q) acc[q] = 0.0f;
+    for (int j0 = jbeg; j0 < jend; j0 += kLctTile) {
+        const int j1 = min(j0 + kLctTile, jend);
+        __syncthreads();                                    // the chunk before has been read
+        if (lane < zn)
+            for (int bb = wave; bb < j1 - j0; bb += kWaves)
+                bins[bb][lane] = a.vol[((size_t)n * a.nr + j0 + bb) * a.H + m0 + lane];
+        __syncthreads();
+        const int lo = max(f, j0), hi = min(f + cnt, j1);
+        for (int j = lo; j < hi; ++j) {
+            const float wj = w[j - f];
+            const float* const row = bins[j - j0];
+#pragma unroll
+            for (int q = 0; q < kLctBinsPerLane; ++q)
+                if (wave + q * kWaves < zn) acc[q] = fmaf(wj, row[wave + q * kWaves], acc[q]);
+        }
+    }
+    const int i = i0 + lane;
+    if (i < a.nv) {
+#pragma unroll
+        for (int q = 0; q < kLctBinsPerLane; ++q) {
+            const int m = m0 + wave + q * kWaves;
+            if (m < a.H) {
+                for (int img = 0; img < 8; ++img) {         // (m, n, i) and its images in the padding
+                    const size_t mm = m + (img & 4 ? a.H : 0), nn = n + (img & 2 ? a.W : 0), ii = i + (img & 1 ? a.nv : 0);
+                    a.pad[(mm * Nx + nn) * Nv + ii] = make_float2(img == 0 ? acc[q] : 0.0f, 0.0f);
+                }
+            }
+        }
+    }
+}
+
+struct LctStoreRowsArgs {
+    const float2* field;   // [Nz][Nx][Nv]
+    const int* perm;
+    const int* first;      // [nr]: the tables of R^T
+    const int* start;      // [nr + 1]
+    const float* weight;   // [nnz]
+    float* rows;           // [H W][nr]
+    int H, W, nr, nv, nnz, sm, sn, power;
+    float r0, dr;
+};
+
+// one workgroup per lattice point (m, n)
+__global__ __launch_bounds__(kBlock) void lct_store_rows_kernel(LctStoreRowsArgs a) {
+    __shared__ float cells[kLctMaxCells];
+    const int m = blockIdx.x / a.W, n = blockIdx.x - m * a.W;
+    const float2* const col = a.field + ((size_t)m * (2 * (size_t)a.W) + n) * (2 * (size_t)a.nv);
+    for (int i = threadIdx.x; i < a.nv; i += kBlock) cells[i] = col[i].x;
+    __syncthreads();
+    int v = m * a.sm + n * a.sn;
+    if (a.perm) v = a.perm[v];
+    v = min(max(v, 0), a.H * a.W - 1);                      // a bad perm entry writes a wrong row, never outside the rows
+    float* const row = a.rows + (size_t)v * a.nr;
+    for (int j = threadIdx.x; j < a.nr; j += kBlock) {
+        const LctRun r = lct_run(a.first, a.start, j, a.nv, a.nnz);
+        float acc = 0.0f;
+        for (int q = 0; q < r.cnt; ++q) acc = fmaf(a.weight[r.s + q], cells[r.f + q], acc);
+        row[j] = acc * lct_weight(a.power, j, a.r0, a.dr);
     }
 }
 
@@ -249,20 +384,24 @@ int lct_check_tables(const int32_t* first, const int32_t* start, const float* we
 
 bool lct_positive(double v) { return v > 0.0 && v <= 3.0e38; }
 
-}  // namespace
-
-extern "C" {
-
-int nlosgr_lct_load(const float* rows, const int32_t* perm, int32_t H, int32_t W, int32_t nr, int32_t nv,
-                    int32_t stride_m, int32_t stride_n, float r0, float dr, int32_t power, const int32_t* first,
-                    const int32_t* start, const float* weight, int32_t nnz, float* pad, void* hip_stream) {
-    if (lct_check_extents(H, W, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
-    if (power < 0 || power > 4) return set_err(NLOSGR_E_INVALID, "LCT power must be in 0..4");
+// the lattice arguments of load, load_rows and store_rows; `lo` is the smallest power the pass takes
+int lct_check_lattice(int32_t H, int32_t W, int32_t stride_m, int32_t stride_n, float r0, float dr, int32_t power,
+                      int32_t lo) {
+    if (power < lo || power > 4)
+        return set_err(NLOSGR_E_INVALID, lo < 0 ? "LCT power must be in -4..4" : "LCT power must be in 0..4");
     if (!lct_positive(dr)) return set_err(NLOSGR_E_INVALID, "dr must be finite and > 0");
     if (!(r0 >= 0.0f && r0 <= 3.0e38f)) return set_err(NLOSGR_E_INVALID, "r0 must be finite and >= 0");
     if (stride_m < 0 || stride_n < 0 ||
         (long long)(H - 1) * stride_m + (long long)(W - 1) * stride_n >= (long long)H * W)
         return set_err(NLOSGR_E_INVALID, "lattice strides must keep m stride_m + n stride_n inside [0, H W)");
+    return NLOSGR_OK;
+}
+
+int lct_load_launch(bool sign, const float* rows, const int32_t* perm, int32_t H, int32_t W, int32_t nr, int32_t nv,
+                    int32_t stride_m, int32_t stride_n, float r0, float dr, int32_t power, const int32_t* first,
+                    const int32_t* start, const float* weight, int32_t nnz, float* pad, void* hip_stream) {
+    if (lct_check_extents(H, W, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lct_check_lattice(H, W, stride_m, stride_n, r0, dr, power, sign ? -4 : 0) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (lct_check_tables(first, start, weight, nnz, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (!rows) return set_err(NLOSGR_E_INVALID, "null rows pointer");
     if (!pad) return set_err(NLOSGR_E_INVALID, "null padded array pointer");
@@ -270,11 +409,12 @@ int nlosgr_lct_load(const float* rows, const int32_t* perm, int32_t H, int32_t W
     LctLoadArgs a;
     a.rows = rows; a.perm = perm; a.first = first; a.start = start; a.weight = weight;
     a.H = H; a.W = W; a.nr = nr; a.nv = nv; a.nnz = nnz; a.sm = stride_m; a.sn = stride_n;
-    a.r0 = r0; a.dr = dr; a.pad = (float4*)pad;
+    a.r0 = r0; a.dr = dr; a.power = power; a.pad = (float4*)pad;
     const unsigned ncol = 4u * (unsigned)H * (unsigned)W;      // <= 2^22
     hipStream_t s = (hipStream_t)hip_stream;
 #define LCT_LOAD(P) hipLaunchKernelGGL(lct_load_kernel<P>, dim3(ncol), dim3(kBlock), 0, s, a)
-    switch (power) {
+    if (sign) LCT_LOAD(kLctSigned);
+    else switch (power) {
         case 0: LCT_LOAD(0); break;
         case 1: LCT_LOAD(1); break;
         case 2: LCT_LOAD(2); break;
@@ -282,6 +422,80 @@ int nlosgr_lct_load(const float* rows, const int32_t* perm, int32_t H, int32_t W
         default: LCT_LOAD(4); break;
     }
 #undef LCT_LOAD
+    HIPCHK(hipGetLastError());
+    return NLOSGR_OK;
+}
+
+int lct_store_launch(bool clamp, const float* field, int32_t H, int32_t W, int32_t nr, int32_t nv, const int32_t* first,
+                     const int32_t* start, const float* weight, int32_t nnz, float* volume, void* hip_stream) {
+    if (lct_check_extents(H, W, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lct_check_tables(first, start, weight, nnz, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (!field) return set_err(NLOSGR_E_INVALID, "null field pointer");
+    if (!volume) return set_err(NLOSGR_E_INVALID, "null volume pointer");
+    if ((uintptr_t)field % 8) return set_err(NLOSGR_E_INVALID, "the field must be 8-byte aligned");
+    if ((const void*)field == (const void*)volume) return set_err(NLOSGR_E_INVALID, "the volume must not alias the field");
+    LctStoreArgs a;
+    a.field = (const float2*)field; a.first = first; a.start = start; a.weight = weight; a.vol = volume;
+    a.H = H; a.W = W; a.nr = nr; a.nv = nv; a.nnz = nnz;
+    const dim3 grid((nr + kLctTile - 1) / kLctTile, (H + kLctTile - 1) / kLctTile, W);
+    if (clamp) hipLaunchKernelGGL(lct_store_kernel<true>, grid, dim3(kBlock), 0, (hipStream_t)hip_stream, a);
+    else hipLaunchKernelGGL(lct_store_kernel<false>, grid, dim3(kBlock), 0, (hipStream_t)hip_stream, a);
+    HIPCHK(hipGetLastError());
+    return NLOSGR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nlosgr_lct_load(const float* rows, const int32_t* perm, int32_t H, int32_t W, int32_t nr, int32_t nv,
+                    int32_t stride_m, int32_t stride_n, float r0, float dr, int32_t power, const int32_t* first,
+                    const int32_t* start, const float* weight, int32_t nnz, float* pad, void* hip_stream) {
+    return lct_load_launch(false, rows, perm, H, W, nr, nv, stride_m, stride_n, r0, dr, power, first, start, weight,
+                           nnz, pad, hip_stream);
+}
+
+int nlosgr_lct_load_rows(const float* rows, const int32_t* perm, int32_t H, int32_t W, int32_t nr, int32_t nv,
+                         int32_t stride_m, int32_t stride_n, float r0, float dr, int32_t power, const int32_t* first,
+                         const int32_t* start, const float* weight, int32_t nnz, float* pad, void* hip_stream) {
+    return lct_load_launch(true, rows, perm, H, W, nr, nv, stride_m, stride_n, r0, dr, power, first, start, weight,
+                           nnz, pad, hip_stream);
+}
+
+int nlosgr_lct_load_volume(const float* volume, int32_t H, int32_t W, int32_t nr, int32_t nv, const int32_t* first,
+                           const int32_t* start, const float* weight, int32_t nnz, float* pad, void* hip_stream) {
+    if (lct_check_extents(H, W, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lct_check_tables(first, start, weight, nnz, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (!volume) return set_err(NLOSGR_E_INVALID, "null volume pointer");
+    if (!pad) return set_err(NLOSGR_E_INVALID, "null padded array pointer");
+    if ((uintptr_t)pad % 8) return set_err(NLOSGR_E_INVALID, "the padded array must be 8-byte aligned");
+    if ((const void*)volume == (const void*)pad)
+        return set_err(NLOSGR_E_INVALID, "the padded array must not alias the volume");
+    LctLoadVolumeArgs a;
+    a.vol = volume; a.first = first; a.start = start; a.weight = weight; a.pad = (float2*)pad;
+    a.H = H; a.W = W; a.nr = nr; a.nv = nv; a.nnz = nnz;
+    const dim3 grid((nv + kLctTile - 1) / kLctTile, (H + kLctTile - 1) / kLctTile, W);
+    hipLaunchKernelGGL(lct_load_volume_kernel, grid, dim3(kBlock), 0, (hipStream_t)hip_stream, a);
+    HIPCHK(hipGetLastError());
+    return NLOSGR_OK;
+}
+
+int nlosgr_lct_store_rows(const float* field, const int32_t* perm, int32_t H, int32_t W, int32_t nr, int32_t nv,
+                          int32_t stride_m, int32_t stride_n, float r0, float dr, int32_t power, const int32_t* first,
+                          const int32_t* start, const float* weight, int32_t nnz, float* rows, void* hip_stream) {
+    if (lct_check_extents(H, W, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lct_check_lattice(H, W, stride_m, stride_n, r0, dr, power, -4) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lct_check_tables(first, start, weight, nnz, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (!field) return set_err(NLOSGR_E_INVALID, "null field pointer");
+    if (!rows) return set_err(NLOSGR_E_INVALID, "null rows pointer");
+    if ((uintptr_t)field % 8) return set_err(NLOSGR_E_INVALID, "the field must be 8-byte aligned");
+    if ((const void*)field == (const void*)rows) return set_err(NLOSGR_E_INVALID, "the rows must not alias the field");
+    LctStoreRowsArgs a;
+    a.field = (const float2*)field; a.perm = perm; a.first = first; a.start = start; a.weight = weight; a.rows = rows;
+    a.H = H; a.W = W; a.nr = nr; a.nv = nv; a.nnz = nnz; a.sm = stride_m; a.sn = stride_n; a.power = power;
+    a.r0 = r0; a.dr = dr;
+    hipLaunchKernelGGL(lct_store_rows_kernel, dim3((unsigned)H * (unsigned)W), dim3(kBlock), 0,
+                       (hipStream_t)hip_stream, a);
     HIPCHK(hipGetLastError());
     return NLOSGR_OK;
 }
@@ -336,19 +550,12 @@ int nlosgr_lct_filter(const float* kf, const float* spec, int32_t H, int32_t W, 
 
 int nlosgr_lct_store(const float* field, int32_t H, int32_t W, int32_t nr, int32_t nv, const int32_t* first,
                      const int32_t* start, const float* weight, int32_t nnz, float* volume, void* hip_stream) {
-    if (lct_check_extents(H, W, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
-    if (lct_check_tables(first, start, weight, nnz, nr, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
-    if (!field) return set_err(NLOSGR_E_INVALID, "null field pointer");
-    if (!volume) return set_err(NLOSGR_E_INVALID, "null volume pointer");
-    if ((uintptr_t)field % 8) return set_err(NLOSGR_E_INVALID, "the field must be 8-byte aligned");
-    if ((const void*)field == (const void*)volume) return set_err(NLOSGR_E_INVALID, "the volume must not alias the field");
-    LctStoreArgs a;
-    a.field = (const float2*)field; a.first = first; a.start = start; a.weight = weight; a.vol = volume;
-    a.H = H; a.W = W; a.nr = nr; a.nv = nv; a.nnz = nnz;
-    const dim3 grid((nr + kLctTile - 1) / kLctTile, (H + kLctTile - 1) / kLctTile, W);
-    hipLaunchKernelGGL(lct_store_kernel, grid, dim3(kBlock), 0, (hipStream_t)hip_stream, a);
-    HIPCHK(hipGetLastError());
-    return NLOSGR_OK;
+    return lct_store_launch(true, field, H, W, nr, nv, first, start, weight, nnz, volume, hip_stream);
+}
+
+int nlosgr_lct_store_volume(const float* field, int32_t H, int32_t W, int32_t nr, int32_t nv, const int32_t* first,
+                            const int32_t* start, const float* weight, int32_t nnz, float* volume, void* hip_stream) {
+    return lct_store_launch(false, field, H, W, nr, nv, first, start, weight, nnz, volume, hip_stream);
 }
 
 }  // extern "C"

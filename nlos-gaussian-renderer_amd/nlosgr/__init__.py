@@ -20,7 +20,8 @@ Layers:
     nlosgr.rsd             fast phasor field (Rayleigh-Sommerfeld diffraction by FFT on the wall's lattice): four HIP
                            passes around torch.fft, rsd_capture; confocal or one laser spot
     nlosgr.lct             light-cone transform of a confocal capture (Wiener-filtered inversion): four HIP passes
-                           around torch.fft, lct_capture
+                           around torch.fft, lct_capture; LctOperator, the confocal forward operator and its adjoint
+                           at FFT speed, lct_solve (Landweber, FISTA), lct_solve_capture
     nlosgr.forward_project its adjoint: voxel grid -> transients, voxel_transient, operator_norm, landweber
                            (both take lasers= for a non-confocal capture: the laser spot differs from the sensed one)
     nlosgr.irf             temporal instrument response: IRF, gaussian_irf, convolve_time (render -> capture)
@@ -35,13 +36,16 @@ __all__ = ["Geometry", "build_geometry", "relay_wall_grid", "volume_box_point", 
            "features_flat", "RenderConfig", "RenderFn", "render", "render_forward", "render_backward", "bboxes",
            "Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply",
            "backproject_capture", "time_filter", "phasor_capture", "phasor_kernel",
-           "fk_capture", "fk_migrate", "rsd_capture", "rsd_reconstruct", "lct_capture", "lct_reconstruct"]
+           "fk_capture", "fk_migrate", "rsd_capture", "rsd_reconstruct", "lct_capture", "lct_reconstruct",
+           "LctOperator", "lct_project", "lct_adjoint", "lct_solve", "lct_solve_capture", "lct_load_volume",
+           "lct_store_rows", "lct_load_rows", "lct_store_volume"]
 
 _BP_NAMES = ("backproject_capture", "time_filter")
 _PH_NAMES = ("phasor_capture", "phasor_kernel")
 _FK_NAMES = ("fk_capture", "fk_migrate")
 _RSD_NAMES = ("rsd_capture", "rsd_reconstruct")
-_LCT_NAMES = ("lct_capture", "lct_reconstruct")
+_LCT_NAMES = ("lct_capture", "lct_reconstruct", "LctOperator", "lct_project", "lct_adjoint", "lct_solve",
+              "lct_solve_capture", "lct_load_volume", "lct_store_rows", "lct_load_rows", "lct_store_volume")
 _MESH_NAMES = ("Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply")
 
 

@@ -122,7 +122,9 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_backproject_phasor", "nlosgr_render_nc_workspace_bytes", "nlosgr_render_nc_fwd", "nlosgr_render_nc_bwd",
            "nlosgr_sgld_noise", "nlosgr_fk_load", "nlosgr_fk_stolt", "nlosgr_fk_store",
            "nlosgr_rsd_load", "nlosgr_rsd_kernel", "nlosgr_rsd_apply", "nlosgr_rsd_gather",
-           "nlosgr_lct_load", "nlosgr_lct_kernel", "nlosgr_lct_filter", "nlosgr_lct_store", "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
+           "nlosgr_lct_load", "nlosgr_lct_kernel", "nlosgr_lct_filter", "nlosgr_lct_store",
+           "nlosgr_lct_load_volume", "nlosgr_lct_store_rows", "nlosgr_lct_load_rows", "nlosgr_lct_store_volume",
+           "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
 _load_error = None
@@ -253,6 +255,14 @@ def load():
     lib.nlosgr_lct_filter.restype = ctypes.c_int
     lib.nlosgr_lct_store.argtypes = [_P, I32, I32, I32, I32, _P, _P, _P, I32, _P, _P]
     lib.nlosgr_lct_store.restype = ctypes.c_int
+    lib.nlosgr_lct_load_volume.argtypes = lib.nlosgr_lct_store.argtypes
+    lib.nlosgr_lct_load_volume.restype = ctypes.c_int
+    lib.nlosgr_lct_store_rows.argtypes = lib.nlosgr_lct_load.argtypes
+    lib.nlosgr_lct_store_rows.restype = ctypes.c_int
+    lib.nlosgr_lct_load_rows.argtypes = lib.nlosgr_lct_load.argtypes
+    lib.nlosgr_lct_load_rows.restype = ctypes.c_int
+    lib.nlosgr_lct_store_volume.argtypes = lib.nlosgr_lct_store.argtypes
+    lib.nlosgr_lct_store_volume.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

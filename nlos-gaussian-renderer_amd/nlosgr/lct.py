@@ -27,10 +27,22 @@ y0 + r0 + j dr, zs[m]) (fk.fk_grid), as for f-k migration.  The FFTs are plumbin
 between them is HIP (csrc/nlosgr_lct.hip).  Bitwise repeatable; the rows may be in any order (perm=).  Confocal only:
 a non-confocal capture goes to nlosgr.phasor or nlosgr.backproject.
 
-No CPU fallback, no backward.
+The same parts run the other way give the confocal measurement operator itself, A: volume [W, nr, H] -> rows, and
+its exact adjoint (LctOperator; include/nlosgr.h, "LCT operator pair"):
+
+    A v   = w . R^T Re ifftn( fftn(pad R v) Fk )                lct_load_volume, lct_filter, lct_store_rows
+    A^T h =     R^T Re ifftn( fftn(pad R (w . h)) conj(Fk) )    lct_load_rows, lct_filter, lct_store_volume
+
+with w_j = (r0 + j dr)^power, power -4..4, and nothing clamped, so both take a residual.  LctOperator.project is
+differentiable (its backward is the adjoint); lct_solve runs projected Landweber or FISTA steps on 1/2 |A v - h|^2 at
+FFT speed on the capture's full lattice, lct_solve_capture does so for a loaded capture, and
+voxel_fit.VoxelFitStep(operator=) fits Gaussians through it.  Not built: regularisers (TV, sparsity), a Poisson data
+term in lct_solve, the non-confocal case.
+
+No CPU fallback.
 
     python -m nlosgr.lct CAPTURE.mat --start S --end E [--power P] [--snr X] [--nv N] [--backprop] --out lct.npz
-        [--mesh lct.ply --level-frac F]
+        [--mesh lct.ply --level-frac F] [--iterations N [--no-accelerate] [--falloff Q]]
 """
 import argparse
 import functools
@@ -144,35 +156,45 @@ def _resampling(res, r0, dr, nr, nv):
     return res
 
 
+def _load(symbol, what, rows, H, W, r0, dr, power, nv, perm, x_along, resampling, out):
+    """lct_load and lct_load_rows: the two instances of one kernel."""
+    lib = _lib.load()
+    rows = _gpu(rows, torch.float32, what)
+    if rows.dim() != 2:
+        raise ValueError(f"nlosgr: {what} takes rows [H W, nr]")
+    H, W, nr = _extents(H, W, rows.shape[1])
+    if rows.shape[0] != H * W:
+        raise ValueError(f"nlosgr: rows must be [{H * W}, nr] for an {H} x {W} lattice")
+    res = _resampling(resampling, r0, dr, nr, nv)
+    dev = rows.device
+    perm, sm, sn = _lattice(perm, x_along, H, W, dev, what)
+    pad = _work(out, (2 * H, 2 * W, 2 * res.nv), dev, what)
+    first, start, weight = res.on(dev)[:3]
+    _lib.check(getattr(lib, symbol)(_lib.ptr(rows), _lib.ptr(perm), H, W, nr, res.nv, sm, sn, float(r0), float(dr),
+                                    int(power), _lib.ptr(first), _lib.ptr(start), _lib.ptr(weight), res.nnz,
+                                    _lib.ptr(pad), _lib.stream_handle(dev)))
+    return pad
+
+
+def _lattice(perm, x_along, H, W, dev, what):
+    """(perm checked, stride_m, stride_n): how lattice point (m, n) finds its row."""
+    if x_along not in X_ALONG:
+        raise ValueError(f"nlosgr: x_along must be one of {X_ALONG}")
+    if perm is not None:
+        perm = _gpu(perm, torch.int32, f"{what} (perm)")
+        if perm.shape != (H * W,) or perm.device != dev:
+            raise ValueError(f"nlosgr: perm must be int32 [{H * W}] on {dev}")
+        if int(perm.min()) < 0 or int(perm.max()) >= H * W:
+            raise ValueError("nlosgr: perm holds a row index outside [0, H W)")
+    return (perm,) + ((W, 1) if x_along == "n" else (1, H))
+
+
 @torch.no_grad()
 def lct_load(rows, H, W, r0, dr, power=4, nv=None, perm=None, x_along="n", resampling=None, out=None):
     """Stage 1, complex64 [2H, 2W, 2nv]: the rows weighted by r^power, resampled to the depth-squared cells and
     zero-padded (nlosgr_lct_load; every element of `out` is written).  perm: int32 [H W], the row that holds lattice
     point v (None: row v).  resampling: lct_resampling(r0, dr, nr, nv), built when not given."""
-    lib = _lib.load()
-    rows = _gpu(rows, torch.float32, "lct_load")
-    if rows.dim() != 2:
-        raise ValueError("nlosgr: lct_load takes rows [H W, nr]")
-    H, W, nr = _extents(H, W, rows.shape[1])
-    if rows.shape[0] != H * W:
-        raise ValueError(f"nlosgr: rows must be [{H * W}, nr] for an {H} x {W} lattice")
-    if x_along not in X_ALONG:
-        raise ValueError(f"nlosgr: x_along must be one of {X_ALONG}")
-    res = _resampling(resampling, r0, dr, nr, nv)
-    dev = rows.device
-    if perm is not None:
-        perm = _gpu(perm, torch.int32, "lct_load (perm)")
-        if perm.shape != (H * W,) or perm.device != dev:
-            raise ValueError(f"nlosgr: perm must be int32 [{H * W}] on {dev}")
-        if int(perm.min()) < 0 or int(perm.max()) >= H * W:
-            raise ValueError("nlosgr: perm holds a row index outside [0, H W)")
-    sm, sn = (W, 1) if x_along == "n" else (1, H)
-    pad = _work(out, (2 * H, 2 * W, 2 * res.nv), dev, "lct_load")
-    first, start, weight = res.on(dev)[:3]
-    _lib.check(lib.nlosgr_lct_load(_lib.ptr(rows), _lib.ptr(perm), H, W, nr, res.nv, sm, sn, float(r0), float(dr),
-                                   int(power), _lib.ptr(first), _lib.ptr(start), _lib.ptr(weight), res.nnz,
-                                   _lib.ptr(pad), _lib.stream_handle(dev)))
-    return pad
+    return _load("nlosgr_lct_load", "lct_load", rows, H, W, r0, dr, power, nv, perm, x_along, resampling, out)
 
 
 def lct_scale(H, W, nv, sx, sz, dv):
@@ -263,20 +285,255 @@ def lct_inverse(H, W, nv, sx, sz, dv, snr, backprop=False, device="cuda"):
     return lct_filter(None, kf=kf, snr=snr, backprop=backprop, out=kf)
 
 
-@torch.no_grad()
-def lct_store(field, resampling):
-    """Stage 6, fp32 [W, nr, H]: max(R^T Re field, 0) of the [0:H, 0:W, 0:nv] corner of field [2H, 2W, 2nv] =
-    ifftn(spec G), with the (cell -> bin, time <-> z) transpose into the voxel order (nlosgr_lct_store)."""
+def _store(symbol, what, field, resampling):
+    """lct_store and lct_store_volume: the two instances of one kernel."""
     lib = _lib.load()
-    field, H, W, nv = _spectrum(field, "lct_store")
+    field, H, W, nv = _spectrum(field, what)
     if not isinstance(resampling, Resampling) or resampling.nv != nv:
         raise ValueError(f"nlosgr: resampling must be lct_resampling's result with nv = {nv}")
     nr = resampling.nr
     first_t, start_t, weight_t = resampling.on(field.device)[3:]
     vol = torch.empty((W, nr, H), dtype=torch.float32, device=field.device)
-    _lib.check(lib.nlosgr_lct_store(_lib.ptr(field), H, W, nr, nv, _lib.ptr(first_t), _lib.ptr(start_t),
-                                    _lib.ptr(weight_t), resampling.nnz, _lib.ptr(vol), _lib.stream_handle(field.device)))
+    _lib.check(getattr(lib, symbol)(_lib.ptr(field), H, W, nr, nv, _lib.ptr(first_t), _lib.ptr(start_t),
+                                    _lib.ptr(weight_t), resampling.nnz, _lib.ptr(vol),
+                                    _lib.stream_handle(field.device)))
     return vol
+
+
+@torch.no_grad()
+def lct_store(field, resampling):
+    """Stage 6, fp32 [W, nr, H]: max(R^T Re field, 0) of the [0:H, 0:W, 0:nv] corner of field [2H, 2W, 2nv] =
+    ifftn(spec G), with the (cell -> bin, time <-> z) transpose into the voxel order (nlosgr_lct_store)."""
+    return _store("nlosgr_lct_store", "lct_store", field, resampling)
+
+
+# ---- the operator pair: A (volume -> rows) and its adjoint, nothing clamped ---------------------------------------
+
+def _power(power):
+    if not -4 <= int(power) <= 4:
+        raise ValueError(f"nlosgr: the LCT operator's power must be in -4..4, got {int(power)}")
+    return int(power)
+
+
+@torch.no_grad()
+def lct_load_rows(rows, H, W, r0, dr, power=0, nv=None, perm=None, x_along="n", resampling=None, out=None):
+    """lct_load for signed rows, complex64 [2H, 2W, 2nv]: R (w rows), w_j = (r0 + j dr)^power with power in -4..4
+    (0 where r <= 0 and power < 0), no clamp (nlosgr_lct_load_rows).  For power 0..4 and rows >= 0 the bits of
+    lct_load.  The first stage of the adjoint."""
+    return _load("nlosgr_lct_load_rows", "lct_load_rows", rows, H, W, r0, dr, _power(power), nv, perm, x_along,
+                 resampling, out)
+
+
+@torch.no_grad()
+def lct_store_volume(field, resampling):
+    """lct_store without the clamp, fp32 [W, nr, H]: R^T Re field, signed (nlosgr_lct_store_volume).  Where the sum
+    is >= 0 the bits of lct_store.  The last stage of the adjoint."""
+    return _store("nlosgr_lct_store_volume", "lct_store_volume", field, resampling)
+
+
+@torch.no_grad()
+def lct_load_volume(volume, resampling, out=None):
+    """The first stage of A, complex64 [2H, 2W, 2nv]: the volume [W, nr, H] resampled along its bins to the
+    depth-squared cells, g[m, n, i] = sum_j R[i, j] volume[n, j, m], transposed into the work array's order and
+    zero-padded (nlosgr_lct_load_volume; every element of `out` is written).  Signed, no weight."""
+    lib = _lib.load()
+    volume = _gpu(volume, torch.float32, "lct_load_volume")
+    if volume.dim() != 3:
+        raise ValueError("nlosgr: lct_load_volume takes a volume [W, nr, H]")
+    H, W, nr = _extents(volume.shape[2], volume.shape[0], volume.shape[1])
+    if not isinstance(resampling, Resampling) or resampling.nr != nr:
+        raise ValueError(f"nlosgr: resampling must be lct_resampling's result with nr = {nr}")
+    dev = volume.device
+    pad = _work(out, (2 * H, 2 * W, 2 * resampling.nv), dev, "lct_load_volume")
+    first, start, weight = resampling.on(dev)[:3]
+    _lib.check(lib.nlosgr_lct_load_volume(_lib.ptr(volume), H, W, nr, resampling.nv, _lib.ptr(first), _lib.ptr(start),
+                                          _lib.ptr(weight), resampling.nnz, _lib.ptr(pad), _lib.stream_handle(dev)))
+    return pad
+
+
+@torch.no_grad()
+def lct_store_rows(field, resampling, power=0, perm=None, x_along="n", out=None):
+    """The last stage of A, fp32 [H W, nr]: rows[v(m, n), j] = w_j sum_i R[i, j] Re field[m, n, i] over the
+    [0:H, 0:W, 0:nv] corner of field [2H, 2W, 2nv], w_j = (r0 + j dr)^power with the resampling's own r0 and dr, power
+    in -4..4 (nlosgr_lct_store_rows).  Signed.  perm, x_along: as lct_load; a row of `out` that no lattice point
+    names is left as it is."""
+    lib = _lib.load()
+    field, H, W, nv = _spectrum(field, "lct_store_rows")
+    if not isinstance(resampling, Resampling) or resampling.nv != nv:
+        raise ValueError(f"nlosgr: resampling must be lct_resampling's result with nv = {nv}")
+    nr, dev = resampling.nr, field.device
+    perm, sm, sn = _lattice(perm, x_along, H, W, dev, "lct_store_rows")
+    if out is None:
+        rows = torch.empty((H * W, nr), dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_contiguous():
+            raise ValueError(f"nlosgr: out must be a contiguous float32 [{H * W}, {nr}] tensor on {dev}")
+        rows = _gpu(out, torch.float32, "lct_store_rows")
+        if tuple(rows.shape) != (H * W, nr) or rows.device != dev:
+            raise ValueError(f"nlosgr: out must be a contiguous float32 [{H * W}, {nr}] tensor on {dev}")
+    first_t, start_t, weight_t = resampling.on(dev)[3:]
+    _lib.check(lib.nlosgr_lct_store_rows(_lib.ptr(field), _lib.ptr(perm), H, W, nr, nv, sm, sn, resampling.r0,
+                                         resampling.dr, _power(power), _lib.ptr(first_t), _lib.ptr(start_t),
+                                         _lib.ptr(weight_t), resampling.nnz, _lib.ptr(rows), _lib.stream_handle(dev)))
+    return rows
+
+
+class LctOperator:
+    """The confocal measurement operator on a wall lattice, A: volume [W, nr, H] -> rows [H W, nr], and its exact
+    adjoint, at FFT speed (include/nlosgr.h, "LCT operator pair"):
+
+        A v   = w . R^T Re ifftn( fftn(pad R v) Fk )            lct_load_volume, lct_filter, lct_store_rows
+        A^T h =     R^T Re ifftn( fftn(pad R (w . h)) conj(Fk) )  lct_load_rows, lct_filter, lct_store_volume
+
+    with w_j = (r0 + j dr)^power, power in -4..4, and nothing clamped, so both take a residual.  The lattice, the
+    window, perm and x_along are lct_reconstruct's.  The resampling and the light cone's spectrum Fk (complex64
+    [2H, 2W, 2nv]: 1 GiB at 128 x 128 x 1024) are built once, and one work array of that size is kept; each call
+    holds one more for the spectrum while it runs.  With power = -3, scale_to_physical * A is forward_project's
+    confocal transient at power -4 on grid() (the cells are not hat splats: smooth volumes agree, a single voxel
+    does not)."""
+
+    def __init__(self, H, W, sx, sz, r0, dr, nr, power=0, nv=None, perm=None, x_along="n", device="cuda"):
+        self.H, self.W, self.nr = _extents(H, W, nr)
+        if not (float(sx) > 0 and float(sz) > 0):
+            raise ValueError("nlosgr: sx and sz must be > 0")
+        self.power = _power(power)
+        self.resampling = lct_resampling(r0, dr, nr, nv)
+        self.nv, self.r0, self.dr = self.resampling.nv, float(r0), float(dr)   # (the kernels take them as fp32)
+        self.sx, self.sz = float(sx), float(sz)
+        self.work = lct_kernel(self.H, self.W, self.nv, sx, sz, self.resampling.dv, device=device)
+        self.device = self.work.device
+        self.Fk = torch.fft.fftn(self.work)
+        self.perm, _, _ = _lattice(perm, x_along, self.H, self.W, self.device, "LctOperator")
+        self.x_along = x_along
+
+    @property
+    def volume_shape(self):
+        return (self.W, self.nr, self.H)
+
+    @property
+    def rows_shape(self):
+        return (self.H * self.W, self.nr)
+
+    @property
+    def scale_to_physical(self):
+        """dv / (2 dr lct_scale): scale_to_physical * A at power -3 is forward_project at power -4, per unit voxel
+        value (the resampling carries one 1 / r, the cell width dv / (2 r) the bin's share, lct_scale the kernel's
+        unit norm)."""
+        dv = self.resampling.dv
+        return dv / (2.0 * self.resampling.dr * lct_scale(self.H, self.W, self.nv, self.sx, self.sz, dv))
+
+    def grid(self, xs, zs, y0):
+        """The VoxelGrid of the operator's volumes (fk.fk_grid, from r0 and dr as they were given)."""
+        return fk_grid(xs, zs, y0, self.r0, self.dr, self.nr)
+
+    @torch.no_grad()
+    def forward(self, volume, out=None):
+        """A volume: rows [H W, nr] fp32, signed."""
+        volume = _gpu(volume, torch.float32, "LctOperator.forward")
+        if tuple(volume.shape) != self.volume_shape or volume.device != self.device:
+            raise ValueError(f"nlosgr: the volume must be float32 {self.volume_shape} on {self.device}")
+        spec = torch.fft.fftn(lct_load_volume(volume, self.resampling, out=self.work))
+        lct_filter(spec, inverse=self.Fk, out=spec)
+        return lct_store_rows(torch.fft.ifftn(spec, out=self.work), self.resampling, power=self.power, perm=self.perm,
+                              x_along=self.x_along, out=out)
+
+    @torch.no_grad()
+    def adjoint(self, rows):
+        """A^T rows: a volume [W, nr, H] fp32, signed."""
+        rows = _gpu(rows, torch.float32, "LctOperator.adjoint")
+        if tuple(rows.shape) != self.rows_shape or rows.device != self.device:
+            raise ValueError(f"nlosgr: the rows must be float32 {self.rows_shape} on {self.device}")
+        spec = torch.fft.fftn(lct_load_rows(rows, self.H, self.W, self.r0, self.dr, power=self.power, perm=self.perm,
+                                            x_along=self.x_along, resampling=self.resampling, out=self.work))
+        lct_filter(spec, kf=self.Fk, backprop=True, out=spec)
+        return lct_store_volume(torch.fft.ifftn(spec, out=self.work), self.resampling)
+
+    def project(self, volume):
+        """forward as a differentiable function of the volume; the backward is adjoint of the upstream rows."""
+        return _LctProjectFn.apply(volume, self)
+
+    @torch.no_grad()
+    def norm(self, iterations=8):
+        """The largest eigenvalue of A^T A by power iteration from the all-ones volume, as
+        forward_project.operator_norm: a float, one host read at the end.  1 / norm is lct_solve's step."""
+        if int(iterations) < 1:
+            raise ValueError("nlosgr: iterations must be >= 1")
+        v = torch.ones(self.volume_shape, device=self.device)
+        lam = None
+        for _ in range(int(iterations)):
+            v = v / v.double().norm().float()
+            v = self.adjoint(self.forward(v))
+            lam = v.double().norm()
+        return float(lam)
+
+
+class _LctProjectFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, volume, op):
+        ctx.op = op
+        return op.forward(volume)
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        return ctx.op.adjoint(grad_rows), None
+
+
+def lct_project(volume, H, W, sx, sz, r0, dr, power=0, nv=None, perm=None, x_along="n"):
+    """A volume in one call: LctOperator(H, W, sx, sz, r0, dr, nr, ...).forward(volume) for a volume [W, nr, H]."""
+    volume = _gpu(volume, torch.float32, "lct_project")
+    if volume.dim() != 3:
+        raise ValueError("nlosgr: lct_project takes a volume [W, nr, H]")
+    return LctOperator(H, W, sx, sz, r0, dr, volume.shape[1], power=power, nv=nv, perm=perm, x_along=x_along,
+                       device=volume.device).forward(volume)
+
+
+def lct_adjoint(rows, H, W, sx, sz, r0, dr, power=0, nv=None, perm=None, x_along="n"):
+    """A^T rows in one call: LctOperator(...).adjoint(rows) for rows [H W, nr]."""
+    rows = _gpu(rows, torch.float32, "lct_adjoint")
+    if rows.dim() != 2:
+        raise ValueError("nlosgr: lct_adjoint takes rows [H W, nr]")
+    return LctOperator(H, W, sx, sz, r0, dr, rows.shape[1], power=power, nv=nv, perm=perm, x_along=x_along,
+                       device=rows.device).adjoint(rows)
+
+
+@torch.no_grad()
+def lct_solve(rows, op, iterations=30, nonneg=True, step=None, x0=None, accelerate=False):
+    """(volume [W, nr, H], objective [iterations]): projected gradient on 1/2 |A v - h|^2 with A = op (an
+    LctOperator), laid out like forward_project.landweber:  x+ = max(y - step A^T (A y - h), 0) (no max without
+    nonneg) from x0 (zeros by default), step = 1 / op.norm() by default.  accelerate=False: y = x+ (Landweber).
+    accelerate=True: FISTA, t+ = (1 + sqrt(1 + 4 t^2)) / 2, y = x+ + ((t - 1) / t+) (x+ - x), t = 1 at the start;
+    the projection is applied to x+, and x+ is what is returned.
+    objective[n] is 1/2 |A y_n - h|^2 at the point y_n where gradient n is taken, BEFORE update n (with FISTA that
+    is the extrapolated point, not the iterate x_n); float64 on the device, no host read inside the loop."""
+    if not isinstance(op, LctOperator):
+        raise TypeError("nlosgr: lct_solve takes an LctOperator")
+    rows = _gpu(rows, torch.float32, "lct_solve")
+    if tuple(rows.shape) != op.rows_shape or rows.device != op.device:
+        raise ValueError(f"nlosgr: the rows must be float32 {op.rows_shape} on {op.device}")
+    step = 1.0 / op.norm() if step is None else float(step)
+    if x0 is None:
+        x = torch.zeros(op.volume_shape, device=rows.device)
+    else:
+        x = _gpu(x0, torch.float32, "lct_solve").clone()
+        if tuple(x.shape) != op.volume_shape:
+            raise ValueError(f"nlosgr: x0 must have the operator's volume shape {op.volume_shape}")
+    objective = torch.zeros(int(iterations), dtype=torch.float64, device=rows.device)
+    res = torch.empty_like(rows)
+    y, t = x.clone(), 1.0
+    for n in range(int(iterations)):
+        op.forward(y, out=res)
+        res.sub_(rows)
+        objective[n] = 0.5 * res.double().square().sum()
+        y.sub_(op.adjoint(res), alpha=step)                 # y is now x+
+        if nonneg:
+            y.clamp_(min=0.0)
+        if accelerate:
+            t_next = (1.0 + np.sqrt(1.0 + 4.0 * t * t)) / 2.0
+            x, y = y, torch.add(y, y - x, alpha=(t - 1.0) / t_next)
+            t = t_next
+        else:
+            x = y
+    return x, objective
 
 
 @torch.no_grad()
@@ -306,16 +563,11 @@ def lct_reconstruct(rows, H, W, sx, sz, r0, dr, power=4, snr=0.8, nv=None, backp
     return lct_store(torch.fft.ifftn(spec), res)
 
 
-@torch.no_grad()
-def lct_capture(data_kwargs, start, end, power=4, snr=0.8, nv=None, backprop=False, crop=True, inverse=None):
-    """The light-cone transform of the capture in data_kwargs (data.make_data_kwargs, shuffled or not) over bins
-    [floor(start), floor(start) + end - start).  crop: keep the voxels inside the capture's volume box, as
-    fk.fk_capture does.  Returns {"volume" [nx,ny,nz], "front", "depth" (voxelize.front_view), "grid"}, the keys of
-    fk_capture.  A non-confocal capture raises NotImplementedError; a wall that is no lattice, wall_lattice's
-    ValueError."""
+def _capture_lattice(data_kwargs, start, end, what):
+    """(rows, H, W, xs, zs, y0, perm, x_along, sx, sz, r0, dr, nr) of a confocal capture on its wall lattice."""
     from .data import is_confocal, volume_target
     if not is_confocal(data_kwargs):
-        raise NotImplementedError("nlosgr: the light-cone transform is confocal only: this capture's laser spots "
+        raise NotImplementedError(f"nlosgr: {what} is confocal only: this capture's laser spots "
                                   "(laser_grid_positions) differ from its sensed points.  Use nlosgr.phasor (or "
                                   "nlosgr.backproject), which take the laser spots")
     I1 = int(np.floor(start))
@@ -326,9 +578,10 @@ def lct_capture(data_kwargs, start, end, power=4, snr=0.8, nv=None, backprop=Fal
     cdt = float(data_kwargs["c"]) * float(data_kwargs["deltaT"])
     sx = lattice_spacing(xs, None if len(xs) > 1 else lattice_spacing(zs))
     sz = lattice_spacing(zs, sx)
-    vol = lct_reconstruct(rows, H, W, sx, sz, I1 * cdt, cdt, power=power, snr=snr, nv=nv, backprop=backprop,
-                          perm=perm.to(rows.device), x_along=x_along, inverse=inverse)
-    grid = fk_grid(xs, zs, y0, I1 * cdt, cdt, nr)
+    return rows, H, W, xs, zs, y0, perm.to(rows.device), x_along, sx, sz, I1 * cdt, cdt, nr
+
+
+def _capture_result(vol, grid, data_kwargs, crop):
     if crop:
         vp = [float(v) for v in data_kwargs["volume_position"]]
         h = float(data_kwargs["volume_size"]) / 2
@@ -339,6 +592,45 @@ def lct_capture(data_kwargs, start, end, power=4, snr=0.8, nv=None, backprop=Fal
     return {"volume": vol, "front": front, "depth": depth, "grid": grid}
 
 
+@torch.no_grad()
+def lct_capture(data_kwargs, start, end, power=4, snr=0.8, nv=None, backprop=False, crop=True, inverse=None):
+    """The light-cone transform of the capture in data_kwargs (data.make_data_kwargs, shuffled or not) over bins
+    [floor(start), floor(start) + end - start).  crop: keep the voxels inside the capture's volume box, as
+    fk.fk_capture does.  Returns {"volume" [nx,ny,nz], "front", "depth" (voxelize.front_view), "grid"}, the keys of
+    fk_capture.  A non-confocal capture raises NotImplementedError; a wall that is no lattice, wall_lattice's
+    ValueError."""
+    rows, H, W, xs, zs, y0, perm, x_along, sx, sz, r0, dr, nr = _capture_lattice(data_kwargs, start, end,
+                                                                                 "the light-cone transform")
+    vol = lct_reconstruct(rows, H, W, sx, sz, r0, dr, power=power, snr=snr, nv=nv, backprop=backprop, perm=perm,
+                          x_along=x_along, inverse=inverse)
+    return _capture_result(vol, fk_grid(xs, zs, y0, r0, dr, nr), data_kwargs, crop)
+
+
+@torch.no_grad()
+def lct_solve_capture(data_kwargs, start, end, falloff=3, power=0, iterations=30, accelerate=True, nv=None,
+                      crop=True):
+    """The non-negative least-squares volume of a confocal capture on its own lattice: lct_solve with
+    LctOperator(power=power) on the rows of bins [floor(start), floor(start) + end - start), bin j multiplied by
+    (r0 + j dr)^falloff first, as voxel_fit.fit_capture does.  Returns the keys of lct_capture plus "objective"
+    [iterations]; crop, and the errors (a non-confocal capture, a wall that is no lattice), as there.
+
+    Why falloff=3 with power=0 is the default, not power=-3 on the raw rows: both state the same physical model
+    (A at power -3 is the confocal transient), but at power -3 the operator carries r^-3 itself, and in a window
+    that starts at r0 = 0 its first bins give it a norm of about 1e11: the step 1 / norm is then so small that the
+    far voxels do not move and the solve stalls.  Moving the r^3 to the rows leaves an operator of norm about 1."""
+    rows, H, W, xs, zs, y0, perm, x_along, sx, sz, r0, dr, nr = _capture_lattice(data_kwargs, start, end,
+                                                                                 "the LCT solver")
+    rows = _gpu(rows.float(), torch.float32, "lct_solve_capture")
+    if falloff:
+        radii = r0 + dr * torch.arange(nr, dtype=torch.float64, device=rows.device)
+        rows = (rows.double() * radii.pow(float(falloff))[None]).float()
+    op = LctOperator(H, W, sx, sz, r0, dr, nr, power=power, nv=nv, perm=perm, x_along=x_along, device=rows.device)
+    vol, objective = lct_solve(rows, op, iterations=iterations, accelerate=accelerate)
+    out = _capture_result(vol, op.grid(xs, zs, y0), data_kwargs, crop)
+    out["objective"] = objective
+    return out
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m nlosgr.lct",
                                  description="Light-cone transform of a confocal capture on its own wall x time "
@@ -346,16 +638,30 @@ def parse_args(argv=None):
     ap.add_argument("capture", help="Zaragoza-format .mat file")
     ap.add_argument("--start", type=int, required=True, help="first time bin")
     ap.add_argument("--end", type=int, required=True, help="one past the last time bin")
-    ap.add_argument("--power", type=int, default=4, choices=range(5), help="falloff compensation r^power")
+    ap.add_argument("--power", type=int, default=None, choices=range(-4, 5),
+                    help="falloff compensation r^power, 0..4 (default 4); with --iterations the operator's power, "
+                         "-4..4 (default 0)")
     ap.add_argument("--snr", type=float, default=0.8, help="signal-to-noise ratio of the Wiener filter")
     ap.add_argument("--nv", type=int, default=None, help="depth-squared cells (default: the number of bins)")
     ap.add_argument("--backprop", action="store_true", help="apply the adjoint, not the Wiener inverse")
+    ap.add_argument("--iterations", type=int, default=0,
+                    help="N > 0: the iterative least-squares volume (lct_solve_capture, N steps on the rows times "
+                         "r^falloff) instead of the Wiener filter; --power is then the operator's (0 unless given)")
+    ap.add_argument("--no-accelerate", dest="accelerate", action="store_false",
+                    help="with --iterations: plain Landweber steps instead of FISTA")
+    ap.add_argument("--falloff", type=float, default=3.0, help="with --iterations: multiply bin j by (r0 + j dr)^falloff")
     ap.add_argument("--out", default="lct.npz")
     ap.add_argument("--mesh", default=None, help="also write the isosurface as a PLY file")
     ap.add_argument("--level-frac", type=float, default=0.5, help="isosurface level as a fraction of the maximum")
     a = ap.parse_args(argv)
     if a.end <= a.start:
         ap.error("--end must be greater than --start")
+    if a.iterations < 0:
+        ap.error("--iterations must be >= 0")
+    if a.power is None:
+        a.power = 0 if a.iterations else 4
+    if not a.iterations and a.power < 0:
+        ap.error("--power must be in 0..4 without --iterations")
     if not a.snr > 0:
         ap.error("--snr must be greater than 0")
     if a.nv is not None and not 1 <= a.nv <= MAX_CELLS:
@@ -370,15 +676,23 @@ def main(argv=None):
         raise RuntimeError("nlosgr: the light-cone transform needs a GPU (no CPU fallback)")
     dev = torch.device("cuda:0")
     dk, *_ = make_data_kwargs(a.capture, dev, shuffle=False)
-    out = lct_capture(dk, a.start, a.end, power=a.power, snr=a.snr, nv=a.nv, backprop=a.backprop)
+    if a.iterations:
+        out = lct_solve_capture(dk, a.start, a.end, falloff=a.falloff, power=a.power, iterations=a.iterations,
+                                accelerate=a.accelerate, nv=a.nv)
+        extra = {"objective": out["objective"].cpu().numpy()}
+        how = f"{a.iterations} {'FISTA' if a.accelerate else 'Landweber'} steps, falloff {a.falloff:g}"
+    else:
+        out = lct_capture(dk, a.start, a.end, power=a.power, snr=a.snr, nv=a.nv, backprop=a.backprop)
+        extra = {}
+        how = "back-projection" if a.backprop else f"snr {a.snr:g}"
     grid, vol = out["grid"], out["volume"]
     vp = dk["volume_position"].cpu().numpy().astype(np.float32)
     # the key names of python -m nlosgr.fk
     np.savez_compressed(a.out, density=vol.cpu().numpy(), albedo=vol.cpu().numpy(), front=out["front"].cpu().numpy(),
                         depth=out["depth"].cpu().numpy(), xs=grid.xs.numpy(), ys=grid.ys.numpy(), zs=grid.zs.numpy(),
-                        cam=np.array([vp[0], 0.0, vp[2]], dtype=np.float32))
+                        cam=np.array([vp[0], 0.0, vp[2]], dtype=np.float32), **extra)
     print(f"wrote {a.out}: {grid.shape} voxels, {dk['camera_grid_positions'].shape[1]} wall points, bins "
-          f"[{a.start}, {a.end}), power {a.power}, {'back-projection' if a.backprop else f'snr {a.snr:g}'}")
+          f"[{a.start}, {a.end}), power {a.power}, {how}")
     if a.mesh:
         from .mesh import isosurface, write_ply
         level = a.level_frac * float(vol.max())

@@ -9,6 +9,8 @@ Two objectives:
             albedo_density) against the capture's rows, A the forward projector (power 0..4, the range of its
             adjoint).  `lasers=` makes it a non-confocal capture: this is how such a capture is fitted with
             Gaussians, since the pair-major renderer is confocal only (data.volume_geometry raises for it).
+            `operator=` (an nlosgr.lct.LctOperator) replaces the pair A, A^T by the LCT operator pair: a confocal
+            capture on a wall lattice, fitted on the lattice's own voxels at FFT speed (fit_capture projector="lct").
 
 VoxelFitStep runs one iteration per call with every piece on the device and no host synchronisation inside:
 voxelize (albedo only) -> project -> loss and dL/drows -> back-project -> voxelize backward -> nlosgr_adam, with
@@ -16,7 +18,7 @@ TrainStep's learning-rate schedule, Adam, regulariser, rebind() and iteration co
 add_new_gs(train_step=) and checkpoint.save_checkpoint(train_step=) take it as they take a TrainStep.
 
     python -m nlosgr.voxel_fit CAPTURE.mat --resolution R --start S --end E --gaussians N --iterations I
-        [--power P --falloff Q --cutoff C] --out CKPT [--recon recon.npz]
+        [--power P --falloff Q --cutoff C] [--projector lct [--nv N]] --out CKPT [--recon recon.npz]
 """
 import argparse
 import math
@@ -44,6 +46,9 @@ class VoxelFitStep:
     target_volume  [nx, ny, nz]: volume mode.  Exactly one of target_volume and rows is given.
     rows, walls, r0, dr, power, lasers   capture mode: rows [nwall, nr] measured at walls [nwall, 3], window and
                    weight as forward_project takes them (power 0..4), lasers as there (None: confocal).
+    rows, operator capture mode through the LCT operator pair: an nlosgr.lct.LctOperator in place of walls=, r0=,
+                   dr=, power= and lasers= (it carries them; passing both raises).  grid must have the operator's
+                   volume shape (W, nr, H) (operator.grid); project is operator.forward, the gradient operator.adjoint.
     irf, loss, rate_floor, gt_times      the fused loss's, as in TrainStep (capture mode only).
     volume_scale   the factor between A(albedo_density) and the rows' units (voxel volume, bin width, gain).
     keep_grads     keep the last step's gradients in self.grads (train.GROUPS order), its volume in self.volume,
@@ -51,13 +56,26 @@ class VoxelFitStep:
 
     def __init__(self, model, grid, cam, preset="cuda", cutoff=3.0, scaling_modifier=1.0, target_volume=None,
                  rows=None, walls=None, r0=None, dr=None, power=0, lasers=None, irf=None, loss="mse", rate_floor=1.0,
-                 gt_times=1.0, volume_scale=1.0, opt=None, spatial_lr_scale=1.0, keep_grads=False, sh_schedule=False):
+                 gt_times=1.0, volume_scale=1.0, opt=None, spatial_lr_scale=1.0, keep_grads=False, sh_schedule=False,
+                 operator=None):
         if not isinstance(grid, VoxelGrid):
             raise TypeError("nlosgr: grid must be a voxelize.VoxelGrid")
         if (target_volume is None) == (rows is None):
             raise ValueError("nlosgr: VoxelFitStep takes exactly one target: target_volume= (volume mode) or rows= "
                              "with walls=, r0=, dr= (capture mode)" + ("; both were given" if rows is not None
                                                                          else "; none was given"))
+        if operator is not None:
+            from .lct import LctOperator
+            if not isinstance(operator, LctOperator):
+                raise TypeError("nlosgr: operator= must be an nlosgr.lct.LctOperator")
+            if rows is None:
+                raise ValueError("nlosgr: operator= belongs to rows= (capture mode), not to target_volume=")
+            if walls is not None or lasers is not None or r0 is not None or dr is not None:
+                raise ValueError("nlosgr: operator= carries the lattice, the window and the power: it cannot be combined "
+                                 "with walls=, lasers=, r0= or dr=")
+            if grid.shape != operator.volume_shape:
+                raise ValueError(f"nlosgr: with operator= the grid must have the operator's volume shape "
+                                 f"{operator.volume_shape} (operator.grid), got {grid.shape}")
         if rows is not None and not 0 <= int(power) <= 4:
             raise ValueError("nlosgr: VoxelFitStep takes a power in 0..4 (the range of backproject, the projector's "
                              f"adjoint), got {int(power)}; scale the rows by r^q for the falloff (fit_capture falloff=)")
@@ -73,13 +91,17 @@ class VoxelFitStep:
         self.cam = torch.as_tensor(cam, dtype=torch.float32).reshape(-1).to(dev).contiguous()
         if self.cam.numel() != 3:
             raise ValueError("nlosgr: cam must have 3 elements")
-        self.target_volume = self.rows = self.walls = self.lasers = None
+        self.target_volume = self.rows = self.walls = self.lasers = self.operator = None
         if target_volume is not None:
             if irf is not None or loss != "mse":
                 raise ValueError("nlosgr: volume mode is the MSE against the volume: irf= and loss= belong to rows=")
             self.target_volume = _gpu_f32(target_volume, "VoxelFitStep")
             if tuple(self.target_volume.shape) != grid.shape:
                 raise ValueError(f"nlosgr: target_volume must have the grid's shape {grid.shape}")
+        elif operator is not None:
+            self.rows, self.operator = _gpu_f32(rows, "VoxelFitStep"), operator
+            if tuple(self.rows.shape) != operator.rows_shape or self.rows.device != operator.device:
+                raise ValueError(f"nlosgr: with operator= the rows must be {operator.rows_shape} on {operator.device}")
         else:
             if walls is None or r0 is None or dr is None:
                 raise ValueError("nlosgr: capture mode needs walls=, r0= and dr= with rows=")
@@ -111,8 +133,11 @@ class VoxelFitStep:
 
     def project(self, volume):
         """volume_scale * A_power(volume): the rows the loss compares with the capture (capture mode)."""
-        rows = forward_project(volume, self.walls, self.grid, self.r0, self.dr, self.rows.shape[1], power=self.power,
-                               lasers=self.lasers)
+        if self.operator is not None:
+            rows = self.operator.forward(volume)
+        else:
+            rows = forward_project(volume, self.walls, self.grid, self.r0, self.dr, self.rows.shape[1],
+                                   power=self.power, lasers=self.lasers)
         return rows if self.volume_scale == 1.0 else rows.mul_(self.volume_scale)
 
     @torch.no_grad()
@@ -128,7 +153,11 @@ class VoxelFitStep:
             rows_pred = self.project(vol)
             loss2, g_rows = fused_loss(rows_pred, self.rows, self.gt_times, irf=self.irf, kind=self.loss_kind,
                                        rate_floor=self.rate_floor)
-            g_vol = backproject(g_rows, self.walls, self.grid, self.r0, self.dr, power=self.power, lasers=self.lasers)
+            if self.operator is not None:
+                g_vol = self.operator.adjoint(g_rows)
+            else:
+                g_vol = backproject(g_rows, self.walls, self.grid, self.r0, self.dr, power=self.power,
+                                    lasers=self.lasers)
             if self.volume_scale != 1.0:
                 g_vol.mul_(self.volume_scale)
         if self.keep_grads:
@@ -137,7 +166,8 @@ class VoxelFitStep:
         return self._finish([d_mu, d_f[:, :1], d_f[:, 1:], d_o, d_s, d_q], loss2, it)
 
 
-def fit_capture(data_kwargs, model, resolution, start, end, power=0, falloff=0, cam=None, **kw):
+def fit_capture(data_kwargs, model, resolution, start, end, power=0, falloff=0, cam=None, projector="exact", nv=None,
+                **kw):
     """The VoxelFitStep of a loaded capture (data.make_data_kwargs), laid out as landweber_capture lays it out:
     bins [floor(start), floor(start) + end - start) of every measurement against VoxelGrid(volume_position,
     volume_size, resolution), r0 = floor(start) c deltaT, dr = c deltaT, the capture's laser spots when it is
@@ -145,7 +175,25 @@ def fit_capture(data_kwargs, model, resolution, start, end, power=0, falloff=0, 
     falloff=q multiplies bin j of the rows by (r0 + j dr)^q first, the compensation the operator's power cannot
     give (it has no negative power).  For a non-confocal capture this compensates the physical (dl ds)^-2 only
     approximately: the bin fixes g = (dl + ds) / 2, and dl ds <= g^2 with equality only where dl = ds; landweber
-    on such a capture has the same limitation.  Further keywords go to VoxelFitStep."""
+    on such a capture has the same limitation.  Further keywords go to VoxelFitStep.
+    projector="lct": through the LCT operator pair instead (VoxelFitStep(operator=)): a confocal capture on a wall
+    lattice (lct.lct_capture's errors otherwise), the grid is the lattice's own fk.fk_grid, uncropped, so resolution
+    is not used; power may be -4..4, nv is the operator's cell count; falloff works as above."""
+    if projector not in ("exact", "lct"):
+        raise ValueError("nlosgr: projector must be 'exact' or 'lct'")
+    if projector == "lct":
+        from .lct import LctOperator, _capture_lattice
+        rows, H, W, xs, zs, y0, perm, x_along, sx, sz, r0, cdt, nr = _capture_lattice(data_kwargs, start, end,
+                                                                                      "the LCT projector")
+        rows = _gpu_f32(rows.float(), "fit_capture")
+        if falloff:
+            radii = r0 + cdt * torch.arange(nr, dtype=torch.float64, device=rows.device)
+            rows = (rows.double() * radii.pow(float(falloff))[None]).float()
+        op = LctOperator(H, W, sx, sz, r0, cdt, nr, power=power, nv=nv, perm=perm, x_along=x_along, device=rows.device)
+        if cam is None:
+            cam = (float(data_kwargs["volume_position"][0]), 0.0, float(data_kwargs["volume_position"][2]))
+        kw.setdefault("irf", data_kwargs.get("irf"))
+        return VoxelFitStep(model, op.grid(xs, zs, y0), cam, rows=rows, operator=op, **kw)
     from .data import volume_target
     I1 = int(np.floor(start))
     nr = int(end - start)
@@ -192,7 +240,14 @@ def parse_args(argv=None):
     ap.add_argument("--end", type=int, required=True, help="one past the last time bin")
     ap.add_argument("--gaussians", type=int, required=True, help="number of Gaussians")
     ap.add_argument("--iterations", type=int, required=True)
-    ap.add_argument("--power", type=int, default=0, choices=range(5), help="weight d^power of the operator")
+    ap.add_argument("--power", type=int, default=0, choices=range(-4, 5),
+                    help="weight d^power of the operator: 0..4 (--projector lct: -4..4)")
+    # (absent from the namespace unless given: a run without them parses to what it did before they existed)
+    ap.add_argument("--projector", choices=("exact", "lct"), default=argparse.SUPPRESS,
+                    help="exact (default): every (voxel, wall point) pair on a --resolution grid; lct: the LCT operator "
+                         "pair on the wall lattice's own voxels (a confocal capture on a lattice)")
+    ap.add_argument("--nv", type=int, default=argparse.SUPPRESS,
+                    help="--projector lct: depth-squared cells (default: the bins)")
     ap.add_argument("--falloff", type=float, default=0.0, help="multiply bin j of the rows by (r0 + j dr)^falloff")
     ap.add_argument("--cutoff", type=float, default=3.0, help="Mahalanobis support radius; <= 0: dense")
     ap.add_argument("--loss", choices=sorted(_lib.LOSSES), default="mse")
@@ -209,6 +264,10 @@ def parse_args(argv=None):
         ap.error("--gaussians must be >= 1")
     if a.resolution < 2:
         ap.error("--resolution must be >= 2")
+    if getattr(a, "projector", "exact") == "exact" and a.power < 0:
+        ap.error("--power must be in 0..4 with --projector exact")
+    if getattr(a, "projector", "exact") == "exact" and hasattr(a, "nv"):
+        ap.error("--nv belongs to --projector lct")
     return a
 
 
@@ -228,7 +287,8 @@ def main(argv=None):
     spacing = float(dk["volume_size"]) / (a.resolution - 1)
     model = model_from_points(pts, rho, spacing)
     step = fit_capture(dk, model, a.resolution, a.start, a.end, power=a.power, falloff=a.falloff, preset="cuda",
-                       cutoff=a.cutoff, loss=a.loss, opt=mcmc_options(a))
+                       cutoff=a.cutoff, loss=a.loss, opt=mcmc_options(a), projector=getattr(a, "projector", "exact"),
+                       nv=getattr(a, "nv", None))
     # one least-squares gain between A(albedo_density) and the rows, from the initial Gaussians (one host read)
     pred = step.project(voxelize(model, step.grid, step.cam, preset="cuda", cutoff=a.cutoff, want_density=False)[1])
     den = float(pred.double().square().sum())
