@@ -267,7 +267,8 @@ NLOSGR_API int nlosgr_rays_fwd(const nlosgr_gaussians* g, const nlosgr_rays* r, 
                     float* density_out, float* trans_out, void* hip_stream);
 
 /* Backward of nlosgr_rays_fwd w.r.t. the RAW parameters (the reference returns zeros,
- * cuda_autograd.py:147-156).  Any of g_rho / g_density / g_trans may be NULL. */
+ * cuda_autograd.py:147-156).  Any of g_rho / g_density / g_trans may be NULL.  nrays == 0 is valid
+ * (filter may then be NULL) and gives all-zero gradients; ng == 0 is valid and writes nothing. */
 NLOSGR_API int nlosgr_rays_bwd(const nlosgr_gaussians* g, const nlosgr_rays* r, const int32_t* filter,
                     float c_deltaT, int32_t use_occlusion, void* workspace, const float* g_rho,
                     const float* g_density, const float* g_trans, float* d_mu, float* d_scaling,

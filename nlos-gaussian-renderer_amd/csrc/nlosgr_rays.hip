@@ -413,7 +413,8 @@ int nlosgr_rays_bwd(const nlosgr_gaussians* g, const nlosgr_rays* r, const int32
     int rc = validate_rays(g, r);
     if (rc) return rc;
     if (g->ng == 0) return NLOSGR_OK;
-    if (!workspace || !filter) return set_err(NLOSGR_E_INVALID, "workspace/filter is null");
+    // (no ray, no filter row: an empty [0, 257] tensor's pointer is null, and the gradients are all zero)
+    if (!workspace || (r->nrays > 0 && !filter)) return set_err(NLOSGR_E_INVALID, "workspace/filter is null");
     if (!d_mu || !d_scaling || !d_rotation || !d_opacity || !d_features)
         return set_err(NLOSGR_E_INVALID, "null gradient output pointer");
     const size_t shm = (size_t)(kMaxPerRay * kGD + 3 * r->nsamp) * sizeof(float);

@@ -75,6 +75,80 @@ def test_rays_analytic_vs_oracle(deg, ng, shift, opac):
     _close(out.cpu(), ref64, 1e-5, 0.0, "analytic per-ray vs the formula in float64")
 
 
+def _clear_hits(o, d, P, t0, t1, sigma=3.0):
+    """bool [nrays, Ng] in float64: the ray's line crosses the Gaussian's sigma-ellipsoid and the clipped section
+    is non-empty, both by a margin fp32 cannot close (so a row made of such Gaussians has exactly that many
+    sections in the kernel too)."""
+    from oracle import torch_ref as R
+    mu, s = P._mu.double(), torch.exp(P._scaling.double())
+    Rt = R.quat_to_rotmat_cuda(P._rotation.double()).transpose(1, 2)
+    so = torch.einsum("gab,rgb->rga", Rt, o.double()[:, None, :] - mu[None]) / s[None]
+    sd = torch.einsum("gab,rb->rga", Rt, d.double()) / s[None]
+    a, b, cc = (sd * sd).sum(-1), 2.0 * (so * sd).sum(-1), (so * so).sum(-1) - sigma * sigma
+    disc = b * b - 4.0 * a * cc
+    sq = torch.sqrt(disc.clamp_min(0.0))
+    te, tx = ((-b - sq) / (2.0 * a)).clamp_min(t0), ((-b + sq) / (2.0 * a)).clamp_max(t1)
+    return (disc > 1e-3 * (b * b + 4.0 * a * cc.abs())) & (tx - te > 1e-3)
+
+
+def test_rays_analytic_section_cap_and_ties():
+    """analytic_kernel at its edges, against the formula in float64 at 1e-5: nrays 5 and 1 (4 rays per workgroup);
+    a ray with exactly 128 sections (kMaxSec) and one with 129, whose last one the cap drops; two identical
+    Gaussians on one ray, whose equal t_enter must rank by filter order (a rank collision would lose a section).
+    The Gaussians are faint (opacity - 4), so no ray reaches the early exit and every section counts."""
+    from nlosgr import GaussianParams, features_flat
+    from nlosgr.rays import render_rays_analytic
+    from oracle import torch_ref as R
+    dev = torch.device("cuda:0")
+    deg, ng = 2, 220
+    m = GaussianParams.synthetic(ng, deg, preset="cuda", device=dev, seed=17)
+    with torch.no_grad():
+        m._scaling.add_(1.0)
+        m._opacity.add_(-4.0)
+        for t in (m._mu, m._scaling, m._rotation, m._opacity, m._features_dc, m._features_rest):
+            t[131] = t[130]                      # two identical Gaussians
+    cam = torch.tensor([0.05, 0.0, -0.1], device=dev)
+    o, d = _ray_grid(cam, 5, 1, dev)
+    P = _oracle_params(m, deg)
+    feats = features_flat(m)
+    t0, t1 = 0.16, 1.44
+    hit = _clear_hits(o.cpu(), d.cpu(), P, t0, t1)
+    assert bool(hit[2, 130]) and bool(hit[2, 131])
+    lists = [torch.nonzero(hit[0]).flatten()[:128].tolist(), torch.nonzero(hit[1]).flatten()[:129].tolist(),
+             [int(torch.nonzero(hit[2]).flatten()[0]), 130, 131, int(torch.nonzero(hit[2]).flatten()[-1])],
+             torch.nonzero(hit[3]).flatten()[::3].tolist(), []]
+    assert [len(x) for x in lists[:3]] == [128, 129, 4]
+    filt = torch.full((5, 257), -1, dtype=torch.int32)
+    for r, idx in enumerate(lists):
+        filt[r, 0] = len(idx)
+        filt[r, 1:1 + len(idx)] = torch.tensor(idx, dtype=torch.int32)
+
+    def ref64(f, rays=slice(None)):
+        return R.render_rays_analytic_batched(o.cpu()[rays], d.cpu()[rays], t0, t1, f, P, feats.detach().cpu(), cam.cpu(),
+                                              deg, dtype=torch.float64)
+
+    def hip(f, rays=slice(None)):
+        return render_rays_analytic(o[rays].contiguous(), d[rays].contiguous(), t0, t1, f.to(dev), m._mu, m._scaling,
+                                    m._rotation, m._opacity, feats, cam, deg, 1.0, 1.28 / 64, 1.0, 3.0).cpu()
+
+    ref = ref64(filt)
+    # the reference sees what the case is about: the 128th section counts, the 129th is dropped, and the second of
+    # the identical Gaussians adds a section of its own
+    cut = filt.clone()
+    cut[0, 0], cut[1, 0], cut[2, 0] = 127, 128, 2
+    rc = ref64(cut)
+    assert abs(float(ref[0] - rc[0])) > 1e-4 * float(ref[0]) and float(ref[1]) == float(rc[1])   # 10 x the tolerance
+    assert abs(float(ref[2] - rc[2])) > 1e-2 * float(ref[2]) and float(ref[4]) == 0.0
+    out = hip(filt)
+    assert float(out[4]) == 0.0
+    _close(out, ref, 1e-5, 0.0, "analytic, 5 rays")
+    for r in range(3):                      # nrays = 1: each ray against its own value
+        one = hip(filt[r:r + 1].contiguous(), slice(r, r + 1))
+        assert one.shape == (1,)
+        _close(one, ref[r:r + 1], 1e-5, 0.0, f"analytic ray {r} alone")
+        assert float(one[0]) == float(out[r])
+
+
 def test_section_renderer_dropin():
     """SectionGaussianRendererCUDA.render_transient: middle-bin placement and broadcast histogram
     (section_renderer.py:163-184) around the per-ray values."""
