@@ -8,6 +8,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "nlosgr_device.hpp"
 
 namespace nlosgr {
@@ -54,6 +56,15 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 __device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ float flog2(float x) { return __builtin_amdgcn_logf(x); }
+
+// f(std::integral_constant<int, v>) for a runtime v in [LO, HI] (a v outside it: HI)
+template <int LO, int HI, class F>
+inline void dispatch_int(int v, F&& f) {
+    if constexpr (LO < HI) {
+        if (v != LO) return dispatch_int<LO + 1, HI>(v, f);
+    }
+    f(std::integral_constant<int, LO>{});
+}
 
 inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 

@@ -6,7 +6,7 @@
 //
 //   nlosgr_fk_load    pad[m][n][j] = (psi, 0),  psi = max(rows[v][j], 0) (r0 + j dr)^power, its square root when
 //                     `amplitude`; zero for m >= H, n >= W or j >= nr.  fp32: r = fma(j, dr, r0), the power as
-//                     r, r r, (r r) r, (r r)(r r), the hardware square root (1 ulp).
+//                     r, r r, (r r) r, (r r)(r r), the hardware square root (1 ulp): fk_psi of nlosgr_lattice.hpp.
 //   nlosgr_fk_stolt   with signed DFT indices c (z), b (x), a (time), gx = Nt dr / (Nx sx), gz = Nt dr / (Nz sz):
 //                         src = sqrt(a^2 + (gx b)^2 + (gz c)^2),  k = floor(src),  f = src - k
 //                         V[c][b][a] = ((1-f) S[c][b][k] + f S[c][b][k+1]) (a / src) exp(-2 pi i (src - a) (r0/dr) / Nt)
@@ -26,14 +26,13 @@
 // row: lanes run along time for the 8-byte reads and along z for the writes (16, 8 or 4 bytes per lane as H
 // divides by 4, 2 or not).
 #include "nlosgr_common.hpp"
-#include "nlosgr_fk.hpp"
+#include "nlosgr_lattice.hpp"
 
 using namespace nlosgr;
 using namespace nlosgr::detail;
 
 namespace {
 
-constexpr int kFkMaxExtent = 1024;   // H, W, nr (voxelize.VoxelGrid's limit: the volume is [W][nr][H])
 constexpr int kFkTile = 64;          // store: tile edge along time and along z
 
 struct FkLoadArgs {
@@ -52,9 +51,7 @@ __global__ __launch_bounds__(kBlock) void fk_load_kernel(FkLoadArgs a) {
     float4* const col = a.pad + (size_t)blockIdx.x * a.nr;
     const float* row = nullptr;
     if (c < a.H && b < a.W) {
-        int v = c * a.sm + b * a.sn;
-        if (a.perm) v = a.perm[v];
-        v = min(max(v, 0), a.H * a.W - 1);      // a bad perm entry reads a wrong row, never outside the rows
+        const int v = lattice_row(a.perm, c, b, a.sm, a.sn, a.H, a.W);
         row = a.rows + (size_t)v * a.nr;
     }
     for (int p = threadIdx.x; p < a.nr; p += kBlock) {
@@ -108,7 +105,7 @@ __device__ __forceinline__ float2 fk_stolt_bin(const float* in, int a, int nr, d
 __global__ __launch_bounds__(kBlock) void fk_stolt_kernel(FkStoltArgs a) {
     const int Nx = 2 * a.W;
     const int ci = blockIdx.x / Nx, bi = blockIdx.x - ci * Nx;
-    const int c = ci < a.H ? ci : ci - 2 * a.H, b = bi < a.W ? bi : bi - Nx;
+    const int c = dft_signed(ci, a.H), b = dft_signed(bi, a.W);
     const double lb = a.gx * (double)b, lc = a.gz * (double)c;
     const double lat2 = lb * lb + lc * lc;
     const float* const in = a.spec + (size_t)blockIdx.x * a.nr * 4;
@@ -163,13 +160,7 @@ __global__ __launch_bounds__(kBlock) void fk_store_kernel(FkStoreArgs a) {
     }
 }
 
-int fk_check_extents(int32_t H, int32_t W, int32_t nr) {
-    if (H < 1 || W < 1 || nr < 1 || H > kFkMaxExtent || W > kFkMaxExtent || nr > kFkMaxExtent)
-        return set_err(NLOSGR_E_INVALID, "f-k extents H, W, nr must be in 1..1024");
-    return NLOSGR_OK;
-}
-
-bool fk_positive(float v) { return v > 0.0f && v <= 3.0e38f; }
+constexpr const char* kFkExtents = "f-k extents H, W, nr";
 
 }  // namespace
 
@@ -178,13 +169,10 @@ extern "C" {
 int nlosgr_fk_load(const float* rows, const int32_t* perm, int32_t H, int32_t W, int32_t nr, int32_t stride_m,
                    int32_t stride_n, float r0, float dr, int32_t power, int32_t amplitude, float* pad,
                    void* hip_stream) {
-    if (fk_check_extents(H, W, nr) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lattice_check_extents(kFkExtents, H, W, nr) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (power < 0 || power > 4) return set_err(NLOSGR_E_INVALID, "f-k power must be in 0..4");
-    if (!fk_positive(dr)) return set_err(NLOSGR_E_INVALID, "dr must be finite and > 0");
-    if (!(r0 >= 0.0f && r0 <= 3.0e38f)) return set_err(NLOSGR_E_INVALID, "r0 must be finite and >= 0");
-    if (stride_m < 0 || stride_n < 0 ||
-        (long long)(H - 1) * stride_m + (long long)(W - 1) * stride_n >= (long long)H * W)
-        return set_err(NLOSGR_E_INVALID, "lattice strides must keep m stride_m + n stride_n inside [0, H W)");
+    if (lattice_check_window(r0, dr) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lattice_check_strides(H, W, stride_m, stride_n) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (!rows) return set_err(NLOSGR_E_INVALID, "null rows pointer");
     if (!pad) return set_err(NLOSGR_E_INVALID, "null padded array pointer");
     if ((uintptr_t)pad % 16) return set_err(NLOSGR_E_INVALID, "the padded array must be 16-byte aligned");
@@ -194,37 +182,23 @@ int nlosgr_fk_load(const float* rows, const int32_t* perm, int32_t H, int32_t W,
     const bool vec2 = nr % 2 == 0 && (uintptr_t)rows % 8 == 0;
     const unsigned ncol = 4u * (unsigned)H * (unsigned)W;      // <= 2^22
     hipStream_t s = (hipStream_t)hip_stream;
-#define FK_LOAD(P, A, V) \
-    hipLaunchKernelGGL((fk_load_kernel<P, A, V>), dim3(ncol), dim3(kBlock), 0, s, a)
-#define FK_LOAD_P(P)                                       \
-    do {                                                   \
-        if (amplitude) {                                   \
-            if (vec2) FK_LOAD(P, true, true);              \
-            else FK_LOAD(P, true, false);                  \
-        } else {                                           \
-            if (vec2) FK_LOAD(P, false, true);             \
-            else FK_LOAD(P, false, false);                 \
-        }                                                  \
-    } while (0)
-    switch (power) {
-        case 0: FK_LOAD_P(0); break;
-        case 1: FK_LOAD_P(1); break;
-        case 2: FK_LOAD_P(2); break;
-        case 3: FK_LOAD_P(3); break;
-        default: FK_LOAD_P(4); break;
-    }
-#undef FK_LOAD_P
-#undef FK_LOAD
+    dispatch_int<0, 4>(power, [&](auto P) {
+        dispatch_int<0, 1>(amplitude != 0, [&](auto AMP) {
+            dispatch_int<0, 1>(vec2, [&](auto VEC2) {
+                hipLaunchKernelGGL((fk_load_kernel<decltype(P)::value, decltype(AMP)::value != 0, decltype(VEC2)::value != 0>),
+                                   dim3(ncol), dim3(kBlock), 0, s, a);
+            });
+        });
+    });
     HIPCHK(hipGetLastError());
     return NLOSGR_OK;
 }
 
 int nlosgr_fk_stolt(const float* spec, int32_t H, int32_t W, int32_t nr, float sx, float sz, float r0, float dr,
                     float* out, void* hip_stream) {
-    if (fk_check_extents(H, W, nr) != NLOSGR_OK) return NLOSGR_E_INVALID;
-    if (!fk_positive(dr)) return set_err(NLOSGR_E_INVALID, "dr must be finite and > 0");
-    if (!(r0 >= 0.0f && r0 <= 3.0e38f)) return set_err(NLOSGR_E_INVALID, "r0 must be finite and >= 0");
-    if (!fk_positive(sx) || !fk_positive(sz)) return set_err(NLOSGR_E_INVALID, "sx and sz must be finite and > 0");
+    if (lattice_check_extents(kFkExtents, H, W, nr) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lattice_check_window(r0, dr) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (!lattice_positive(sx) || !lattice_positive(sz)) return set_err(NLOSGR_E_INVALID, "sx and sz must be finite and > 0");
     if (!spec) return set_err(NLOSGR_E_INVALID, "null spectrum pointer");
     if (!out) return set_err(NLOSGR_E_INVALID, "null migrated spectrum pointer");
     if (out == spec) return set_err(NLOSGR_E_INVALID, "the migrated spectrum must not alias the spectrum");
@@ -242,7 +216,7 @@ int nlosgr_fk_stolt(const float* spec, int32_t H, int32_t W, int32_t nr, float s
 }
 
 int nlosgr_fk_store(const float* field, int32_t H, int32_t W, int32_t nr, float* volume, void* hip_stream) {
-    if (fk_check_extents(H, W, nr) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lattice_check_extents(kFkExtents, H, W, nr) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (!field) return set_err(NLOSGR_E_INVALID, "null field pointer");
     if (!volume) return set_err(NLOSGR_E_INVALID, "null volume pointer");
     if ((uintptr_t)field % 8) return set_err(NLOSGR_E_INVALID, "the field must be 8-byte aligned");

@@ -3,14 +3,14 @@
 // inverse FFT -> resampled back to time bins.  The FFTs themselves are the caller's (torch.fft: hipFFT); this
 // library links the HIP runtime alone.  The work arrays are complex64 [Nz][Nx][Nv] (interleaved re, im) with
 // Nz = 2 H, Nx = 2 W, Nv = 2 nv; lattice point (m, n) is measured at (xs[n], y0, zs[m]) and its row is
-// rows[perm[m sm + n sn]] (perm NULL: rows[m sm + n sn]), as in nlosgr_fk.hip.
+// rows[perm[m sm + n sn]] (perm NULL: rows[m sm + n sn]): lattice_row of nlosgr_lattice.hpp, as in nlosgr_fk.hip.
 //
 // The resampling operator R [nv][nr] between time bins j and depth-squared cells i (include/nlosgr.h) comes as run
 // tables built by the caller in double: row i of R holds weight[start[i] .. start[i+1]) at bins first[i], first[i]
 // + 1, ...; the tables of R^T give, per bin j, its run of cells.  Every row and column is one contiguous run.
 //
 //   nlosgr_lct_load    pad[m][n][i] = (sum_j R[i][j] psi[j], 0), psi = max(rows[v][j], 0) (r0 + j dr)^power (fk_psi
-//                      without the square root, nlosgr_fk.hpp), j ascending, acc = fmaf(w, psi, acc);
+//                      without the square root, nlosgr_lattice.hpp), j ascending, acc = fmaf(w, psi, acc);
 //                      zero for m >= H, n >= W or i >= nv.
 //   nlosgr_lct_kernel  with signed DFT indices c (z), b (x): s = ((b sx)^2 + (c sz)^2) / dv, k = floor(s), f = s - k
 //                      in fp64 without contraction; K[c][b][k] = (float)(scale (1 - f)) where k <= nv - 1,
@@ -50,14 +50,13 @@
 // store_rows needs no transpose: a workgroup stages the nv real parts of one lattice column in LDS and lanes run
 // along j.
 #include "nlosgr_common.hpp"
-#include "nlosgr_fk.hpp"
+#include "nlosgr_lattice.hpp"
 
 using namespace nlosgr;
 using namespace nlosgr::detail;
 
 namespace {
 
-constexpr int kLctMaxExtent = 1024;  // H, W, nr (voxelize.VoxelGrid's limit: the volume is [W][nr][H])
 constexpr int kLctMaxCells = 2048;   // nv
 constexpr int kLctTile = 64;         // store: tile edge along bins and along z, and the chunk of cells
 constexpr int kLctBinsPerLane = kLctTile / kWaves;
@@ -89,14 +88,12 @@ struct LctLoadArgs {
 
 constexpr int kLctSigned = -1;  // lct_load_kernel<kLctSigned>: no clamp, the power (-4..4) from the arguments
 
-// (r0 + j dr)^power, power in -4..4: fk_psi's r and its multiplications; 1 / r^|power| by one IEEE division, 0 where
-// r <= 0
+// (r0 + j dr)^power, power in -4..4: fk_psi's r and its multiplications (nlosgr_lattice.hpp); 1 / r^|power| by one
+// IEEE division, 0 where r <= 0
 __device__ __forceinline__ float lct_weight(int power, int j, float r0, float dr) {
 #pragma clang fp contract(off)
-    const float r = fmaf((float)j, dr, r0);
-    const float r2 = r * r;
-    const int p = power < 0 ? -power : power;
-    const float w = p == 0 ? 1.0f : (p == 1 ? r : (p == 2 ? r2 : (p == 3 ? r2 * r : r2 * r2)));
+    const float r = bin_radius(j, r0, dr);
+    const float w = radius_power(r, power);
     if (power >= 0) return w;
     return r > 0.0f ? 1.0f / w : 0.0f;
 }
@@ -110,16 +107,13 @@ __device__ __forceinline__ float lct_cell(const LctLoadArgs& a, const float* psi
 
 template <int POWER>
 __global__ __launch_bounds__(kBlock) void lct_load_kernel(LctLoadArgs a) {
-    __shared__ float psi[kLctMaxExtent];
+    __shared__ float psi[kLatticeMaxExtent];
     const int Nx = 2 * a.W;
     const int c = blockIdx.x / Nx, b = blockIdx.x - c * Nx;
     float4* const col = a.pad + (size_t)blockIdx.x * a.nv;
     const bool inside = c < a.H && b < a.W;                 // the same for the whole workgroup
     if (inside) {
-        int v = c * a.sm + b * a.sn;
-        if (a.perm) v = a.perm[v];
-        v = min(max(v, 0), a.H * a.W - 1);                  // a bad perm entry reads a wrong row, never outside the rows
-        const float* const row = a.rows + (size_t)v * a.nr;
+        const float* const row = a.rows + (size_t)lattice_row(a.perm, c, b, a.sm, a.sn, a.H, a.W) * a.nr;
         for (int j = threadIdx.x; j < a.nr; j += kBlock) {
             if constexpr (POWER == kLctSigned) psi[j] = row[j] * lct_weight(a.power, j, a.r0, a.dr);
             else psi[j] = fk_psi<POWER, false>(row[j], j, a.r0, a.dr);
@@ -147,7 +141,7 @@ __global__ __launch_bounds__(kBlock) void lct_kernel_kernel(LctKernelArgs a) {
 #pragma clang fp contract(off)
     const int Nx = 2 * a.W;
     const int ci = blockIdx.x / Nx, bi = blockIdx.x - ci * Nx;
-    const int c = ci < a.H ? ci : ci - 2 * a.H, b = bi < a.W ? bi : bi - Nx;
+    const int c = dft_signed(ci, a.H), b = dft_signed(bi, a.W);
     const double lb = a.sx * (double)b, lc = a.sz * (double)c;
     const double s = (lb * lb + lc * lc) / a.dv;
     const double kf = floor(s);
@@ -356,10 +350,7 @@ __global__ __launch_bounds__(kBlock) void lct_store_rows_kernel(LctStoreRowsArgs
     const float2* const col = a.field + ((size_t)m * (2 * (size_t)a.W) + n) * (2 * (size_t)a.nv);
     for (int i = threadIdx.x; i < a.nv; i += kBlock) cells[i] = col[i].x;
     __syncthreads();
-    int v = m * a.sm + n * a.sn;
-    if (a.perm) v = a.perm[v];
-    v = min(max(v, 0), a.H * a.W - 1);                      // a bad perm entry writes a wrong row, never outside the rows
-    float* const row = a.rows + (size_t)v * a.nr;
+    float* const row = a.rows + (size_t)lattice_row(a.perm, m, n, a.sm, a.sn, a.H, a.W) * a.nr;
     for (int j = threadIdx.x; j < a.nr; j += kBlock) {
         const LctRun r = lct_run(a.first, a.start, j, a.nv, a.nnz);
         float acc = 0.0f;
@@ -369,8 +360,7 @@ __global__ __launch_bounds__(kBlock) void lct_store_rows_kernel(LctStoreRowsArgs
 }
 
 int lct_check_extents(int32_t H, int32_t W, int32_t nr, int32_t nv) {
-    if (H < 1 || W < 1 || nr < 1 || H > kLctMaxExtent || W > kLctMaxExtent || nr > kLctMaxExtent)
-        return set_err(NLOSGR_E_INVALID, "LCT extents H, W, nr must be in 1..1024");
+    if (lattice_check_extents("LCT extents H, W, nr", H, W, nr) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (nv < 1 || nv > kLctMaxCells) return set_err(NLOSGR_E_INVALID, "LCT cell count nv must be in 1..2048");
     return NLOSGR_OK;
 }
@@ -382,19 +372,13 @@ int lct_check_tables(const int32_t* first, const int32_t* start, const float* we
     return NLOSGR_OK;
 }
 
-bool lct_positive(double v) { return v > 0.0 && v <= 3.0e38; }
-
 // the lattice arguments of load, load_rows and store_rows; `lo` is the smallest power the pass takes
 int lct_check_lattice(int32_t H, int32_t W, int32_t stride_m, int32_t stride_n, float r0, float dr, int32_t power,
                       int32_t lo) {
     if (power < lo || power > 4)
         return set_err(NLOSGR_E_INVALID, lo < 0 ? "LCT power must be in -4..4" : "LCT power must be in 0..4");
-    if (!lct_positive(dr)) return set_err(NLOSGR_E_INVALID, "dr must be finite and > 0");
-    if (!(r0 >= 0.0f && r0 <= 3.0e38f)) return set_err(NLOSGR_E_INVALID, "r0 must be finite and >= 0");
-    if (stride_m < 0 || stride_n < 0 ||
-        (long long)(H - 1) * stride_m + (long long)(W - 1) * stride_n >= (long long)H * W)
-        return set_err(NLOSGR_E_INVALID, "lattice strides must keep m stride_m + n stride_n inside [0, H W)");
-    return NLOSGR_OK;
+    if (lattice_check_window(r0, (double)dr) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    return lattice_check_strides(H, W, stride_m, stride_n);
 }
 
 int lct_load_launch(bool sign, const float* rows, const int32_t* perm, int32_t H, int32_t W, int32_t nr, int32_t nv,
@@ -412,16 +396,9 @@ int lct_load_launch(bool sign, const float* rows, const int32_t* perm, int32_t H
     a.r0 = r0; a.dr = dr; a.power = power; a.pad = (float4*)pad;
     const unsigned ncol = 4u * (unsigned)H * (unsigned)W;      // <= 2^22
     hipStream_t s = (hipStream_t)hip_stream;
-#define LCT_LOAD(P) hipLaunchKernelGGL(lct_load_kernel<P>, dim3(ncol), dim3(kBlock), 0, s, a)
-    if (sign) LCT_LOAD(kLctSigned);
-    else switch (power) {
-        case 0: LCT_LOAD(0); break;
-        case 1: LCT_LOAD(1); break;
-        case 2: LCT_LOAD(2); break;
-        case 3: LCT_LOAD(3); break;
-        default: LCT_LOAD(4); break;
-    }
-#undef LCT_LOAD
+    dispatch_int<kLctSigned, 4>(sign ? kLctSigned : power, [&](auto P) {
+        hipLaunchKernelGGL(lct_load_kernel<decltype(P)::value>, dim3(ncol), dim3(kBlock), 0, s, a);
+    });
     HIPCHK(hipGetLastError());
     return NLOSGR_OK;
 }
@@ -503,9 +480,10 @@ int nlosgr_lct_store_rows(const float* field, const int32_t* perm, int32_t H, in
 int nlosgr_lct_kernel(int32_t H, int32_t W, int32_t nv, float sx, float sz, double dv, double scale, float* K,
                       void* hip_stream) {
     if (lct_check_extents(H, W, 1, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
-    if (!lct_positive(sx) || !lct_positive(sz)) return set_err(NLOSGR_E_INVALID, "sx and sz must be finite and > 0");
-    if (!lct_positive(dv)) return set_err(NLOSGR_E_INVALID, "dv must be finite and > 0");
-    if (!lct_positive(scale)) return set_err(NLOSGR_E_INVALID, "the kernel's scale must be finite and > 0");
+    if (!lattice_positive((double)sx) || !lattice_positive((double)sz))   // (in double, as dv and scale are)
+        return set_err(NLOSGR_E_INVALID, "sx and sz must be finite and > 0");
+    if (!lattice_positive(dv)) return set_err(NLOSGR_E_INVALID, "dv must be finite and > 0");
+    if (!lattice_positive(scale)) return set_err(NLOSGR_E_INVALID, "the kernel's scale must be finite and > 0");
     if (!K) return set_err(NLOSGR_E_INVALID, "null kernel array pointer");
     if ((uintptr_t)K % 16) return set_err(NLOSGR_E_INVALID, "the kernel array must be 16-byte aligned");
     LctKernelArgs a;
@@ -521,7 +499,8 @@ int nlosgr_lct_filter(const float* kf, const float* spec, int32_t H, int32_t W, 
     if (lct_check_extents(H, W, 1, nv) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (mode < kLctWiener || mode > kLctGiven)
         return set_err(NLOSGR_E_INVALID, "LCT filter mode must be 0 (Wiener), 1 (back-projection) or 2 (a given inverse)");
-    if (mode == kLctWiener && !lct_positive(snr)) return set_err(NLOSGR_E_INVALID, "snr must be finite and > 0");
+    if (mode == kLctWiener && !lattice_positive((double)snr))
+        return set_err(NLOSGR_E_INVALID, "snr must be finite and > 0");
     if (!kf) return set_err(NLOSGR_E_INVALID, "null kernel spectrum pointer");
     if (!out) return set_err(NLOSGR_E_INVALID, "null filter output pointer");
     if (!spec && mode == kLctGiven)

@@ -1,11 +1,9 @@
 // What the voxel gather (nlosgr_backproject.hip: back-projection of confocal, non-confocal and phasor-field
 // captures) and the voxel scatter (nlosgr_forward_project.hip: their adjoint) both use: where a pair's laser
 // distance comes from, the distances and weights of a (voxel, measurement) pair, the grid part of a kernel's
-// arguments, the host checks with their error texts, and the dispatch of a runtime integer to a template
-// argument.  Code that one of the two files uses alone lives in that file.
+// arguments, and the host checks with their error texts.  Code that one of the two files uses alone lives in
+// that file.
 #pragma once
-#include <type_traits>
-
 #include "nlosgr_common.hpp"
 
 namespace nlosgr {
@@ -94,15 +92,6 @@ inline int check_nlaser(int mode, int32_t nlaser, int32_t nmeas) {
     if (mode != kConfocal && nlaser != 1 && nlaser != nmeas)
         return set_err(NLOSGR_E_INVALID, "nlaser must be 1 or nmeas");
     return NLOSGR_OK;
-}
-
-// f(std::integral_constant<int, v>) for a runtime v in [LO, HI] (a v outside it: HI)
-template <int LO, int HI, class F>
-inline void dispatch_int(int v, F&& f) {
-    if constexpr (LO < HI) {
-        if (v != LO) return dispatch_int<LO + 1, HI>(v, f);
-    }
-    f(std::integral_constant<int, LO>{});
 }
 
 }  // namespace detail

@@ -23,13 +23,13 @@
 //
 // No atomics; every output element is written by exactly one lane from the inputs alone: bitwise repeatable.
 #include "nlosgr_common.hpp"
+#include "nlosgr_lattice.hpp"
 
 using namespace nlosgr;
 using namespace nlosgr::detail;
 
 namespace {
 
-constexpr int kRsdMaxExtent = 1024;  // H, W, ny (voxelize.VoxelGrid's limit: the volume is [W][ny][H])
 constexpr int kRsdMaxNt = 8192;      // DFT length of the rows
 constexpr int kRsdMaxBand = 512;     // frequencies in the band
 constexpr int kRsdTile = 32;         // load, gather: tile edge
@@ -68,9 +68,7 @@ __global__ __launch_bounds__(kBlock) void rsd_load_kernel(RsdLoadArgs a) {
         for (int nn = t >> 5; nn < kRsdTile; nn += kBlock / 32) {
             const int n = n0 + nn;
             if (n < a.W && q < a.nq) {
-                int v = m * a.sm + n * a.sn;
-                if (a.perm) v = a.perm[v];
-                v = min(max(v, 0), a.H * a.W - 1);   // a bad perm entry reads a wrong row, never outside the rows
+                const int v = lattice_row(a.perm, m, n, a.sm, a.sn, a.H, a.W);
                 const float2 s = a.spec[(size_t)v * a.nf + a.q_lo + q];
                 const float2 c = a.coef[q];
                 tile[nn][qq] = make_float2(fmaf(c.x, s.x, -(c.y * s.y)), fmaf(c.x, s.y, c.y * s.x));
@@ -101,7 +99,7 @@ __global__ __launch_bounds__(kBlock) void rsd_kernel_kernel(RsdKernelArgs a) {
     if (idx >= npair) return;
     const int j = blockIdx.y;
     const int ai = (int)(idx / (unsigned)a.W), pb = (int)(idx - (unsigned)ai * (unsigned)a.W);
-    const int ap = ai < a.H ? ai : ai - 2 * a.H;
+    const int ap = dft_signed(ai, a.H);
     const double D = (double)a.ys[a.j0 + j] - (double)a.y0;
     const double za = (double)ap * a.sz;
     double x[2];
@@ -109,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void rsd_kernel_kernel(RsdKernelArgs a) {
     bool zero[2];
     for (int e = 0; e < 2; ++e) {
         const int bi = 2 * pb + e;
-        const int bp = bi < a.W ? bi : bi - 2 * a.W;
+        const int bp = dft_signed(bi, a.W);
         zero[e] = ap == -a.H || bp == -a.W;
         const double xb = (double)bp * a.sx;
         const double d = sqrt(za * za + xb * xb + D * D);
@@ -206,13 +204,7 @@ __global__ __launch_bounds__(kRsdGatherBlock) void rsd_gather_kernel(RsdGatherAr
     }
 }
 
-bool rsd_positive(float v) { return v > 0.0f && v <= 3.0e38f; }
-
-int rsd_check_lattice(int32_t H, int32_t W) {
-    if (H < 1 || W < 1 || H > kRsdMaxExtent || W > kRsdMaxExtent)
-        return set_err(NLOSGR_E_INVALID, "RSD lattice extents H, W must be in 1..1024");
-    return NLOSGR_OK;
-}
+constexpr const char* kRsdExtents = "RSD lattice extents H, W";
 
 int rsd_check_band(int32_t Nt, int32_t q_lo, int32_t nq) {
     if (Nt < 2 || Nt > kRsdMaxNt || Nt % 2) return set_err(NLOSGR_E_INVALID, "Nt must be even and in 2..8192");
@@ -222,7 +214,7 @@ int rsd_check_band(int32_t Nt, int32_t q_lo, int32_t nq) {
 }
 
 int rsd_check_planes(int32_t ny, int32_t j0, int32_t nj) {
-    if (ny < 1 || ny > kRsdMaxExtent) return set_err(NLOSGR_E_INVALID, "ny must be in 1..1024");
+    if (ny < 1 || ny > kLatticeMaxExtent) return set_err(NLOSGR_E_INVALID, "ny must be in 1..1024");
     if (j0 < 0 || nj < 1 || (long long)j0 + nj > ny)
         return set_err(NLOSGR_E_INVALID, "the depth planes [j0, j0 + nj) must lie in [0, ny) and hold at least one");
     return NLOSGR_OK;
@@ -239,11 +231,9 @@ extern "C" {
 
 int nlosgr_rsd_load(const float* spec, const int32_t* perm, const float* coef, int32_t H, int32_t W, int32_t Nt,
                     int32_t q_lo, int32_t nq, int32_t stride_m, int32_t stride_n, float* pw, void* hip_stream) {
-    if (rsd_check_lattice(H, W) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lattice_check_extents(kRsdExtents, H, W, 1) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (rsd_check_band(Nt, q_lo, nq) != NLOSGR_OK) return NLOSGR_E_INVALID;
-    if (stride_m < 0 || stride_n < 0 ||
-        (long long)(H - 1) * stride_m + (long long)(W - 1) * stride_n >= (long long)H * W)
-        return set_err(NLOSGR_E_INVALID, "lattice strides must keep m stride_m + n stride_n inside [0, H W)");
+    if (lattice_check_strides(H, W, stride_m, stride_n) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (!spec) return set_err(NLOSGR_E_INVALID, "null spectrum pointer");
     if (!coef) return set_err(NLOSGR_E_INVALID, "null band coefficient pointer");
     if (!pw) return set_err(NLOSGR_E_INVALID, "null padded image pointer");
@@ -261,12 +251,12 @@ int nlosgr_rsd_load(const float* spec, const int32_t* perm, const float* coef, i
 int nlosgr_rsd_kernel(const float* ys, int32_t ny, int32_t j0, int32_t nj, float y0, int32_t H, int32_t W, float sx,
                       float sz, float dr, int32_t Nt, int32_t q_lo, int32_t nq, int32_t power, int32_t laser,
                       float* K, void* hip_stream) {
-    if (rsd_check_lattice(H, W) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lattice_check_extents(kRsdExtents, H, W, 1) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (rsd_check_planes(ny, j0, nj) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (rsd_check_band(Nt, q_lo, nq) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (power < 0 || power > 4) return set_err(NLOSGR_E_INVALID, "RSD power must be in 0..4");
-    if (!rsd_positive(dr)) return set_err(NLOSGR_E_INVALID, "dr must be finite and > 0");
-    if (!rsd_positive(sx) || !rsd_positive(sz)) return set_err(NLOSGR_E_INVALID, "sx and sz must be finite and > 0");
+    if (!lattice_positive(dr)) return set_err(NLOSGR_E_INVALID, "dr must be finite and > 0");
+    if (!lattice_positive(sx) || !lattice_positive(sz)) return set_err(NLOSGR_E_INVALID, "sx and sz must be finite and > 0");
     if (!(y0 >= -3.0e38f && y0 <= 3.0e38f)) return set_err(NLOSGR_E_INVALID, "y0 must be finite");
     if (!ys) return set_err(NLOSGR_E_INVALID, "null depth table pointer");
     if (!K) return set_err(NLOSGR_E_INVALID, "null kernel array pointer");
@@ -285,8 +275,8 @@ int nlosgr_rsd_kernel(const float* ys, int32_t ny, int32_t j0, int32_t nj, float
 
 int nlosgr_rsd_apply(const float* kf, const float* pf, int32_t nj, int32_t nq, int32_t H, int32_t W, float* out,
                      void* hip_stream) {
-    if (rsd_check_lattice(H, W) != NLOSGR_OK) return NLOSGR_E_INVALID;
-    if (nj < 1 || nj > kRsdMaxExtent) return set_err(NLOSGR_E_INVALID, "the number of depth planes must be in 1..1024");
+    if (lattice_check_extents(kRsdExtents, H, W, 1) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (nj < 1 || nj > kLatticeMaxExtent) return set_err(NLOSGR_E_INVALID, "the number of depth planes must be in 1..1024");
     if (nq < 1 || nq > kRsdMaxBand) return set_err(NLOSGR_E_INVALID, "the band must hold 1..512 frequencies");
     if (!kf) return set_err(NLOSGR_E_INVALID, "null kernel spectrum pointer");
     if (!pf) return set_err(NLOSGR_E_INVALID, "null image spectrum pointer");
@@ -311,11 +301,11 @@ int nlosgr_rsd_gather(const float* field, int32_t H, int32_t W, int32_t nq, int3
                       int32_t power, const float* xs, const float* ys, const float* zs, int32_t ny, int32_t j0,
                       int32_t nj, int32_t laser, float lx, float ly, float lz, float* planes, float* mag,
                       void* hip_stream) {
-    if (rsd_check_lattice(H, W) != NLOSGR_OK) return NLOSGR_E_INVALID;
+    if (lattice_check_extents(kRsdExtents, H, W, 1) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (rsd_check_planes(ny, j0, nj) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (rsd_check_band(Nt, q_lo, nq) != NLOSGR_OK) return NLOSGR_E_INVALID;
     if (power < 0 || power > 4) return set_err(NLOSGR_E_INVALID, "RSD power must be in 0..4");
-    if (!rsd_positive(dr)) return set_err(NLOSGR_E_INVALID, "dr must be finite and > 0");
+    if (!lattice_positive(dr)) return set_err(NLOSGR_E_INVALID, "dr must be finite and > 0");
     if (laser && !(fabsf(lx) <= 3.0e38f && fabsf(ly) <= 3.0e38f && fabsf(lz) <= 3.0e38f))
         return set_err(NLOSGR_E_INVALID, "the laser spot must be finite");
     if (!field) return set_err(NLOSGR_E_INVALID, "null field pointer");

@@ -22,6 +22,8 @@ Layers:
     nlosgr.lct             light-cone transform of a confocal capture (Wiener-filtered inversion): four HIP passes
                            around torch.fft, lct_capture; LctOperator, the confocal forward operator and its adjoint
                            at FFT speed, lct_solve (Landweber, FISTA), lct_solve_capture
+    nlosgr.lattice         the wall's lattice that fk, rsd and lct share: wall_lattice, the row lookup, the capture
+                           prologue and crop
     nlosgr.forward_project its adjoint: voxel grid -> transients, voxel_transient, operator_norm, landweber
                            (both take lasers= for a non-confocal capture: the laser spot differs from the sensed one)
     nlosgr.irf             temporal instrument response: IRF, gaussian_irf, convolve_time (render -> capture)

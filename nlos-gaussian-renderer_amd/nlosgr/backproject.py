@@ -25,14 +25,13 @@ No CPU fallback, no backward.
     python -m nlosgr.backproject CAPTURE.mat --resolution 128 --start S --end E [--power P]
         [--filter none|laplacian|log] [--sigma-bins B] --out bp.npz [--mesh bp.ply --level-frac F]
 """
-import argparse
 import ctypes
 import math
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _cli, _lib
 from .irf import IRF, irf_apply
 from .voxelize import VoxelGrid, front_view
 
@@ -155,47 +154,21 @@ def backproject_capture(data_kwargs, resolution, start, end, power=0, filter="lo
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m nlosgr.backproject",
-                                 description="Back-project a confocal or non-confocal capture (the optional field "
-                                             "laserGridPositions) onto a voxel grid (volume, front view, depth).")
-    ap.add_argument("capture", help="Zaragoza-format .mat file")
+    ap = _cli.capture_parser("python -m nlosgr.backproject", "bp.npz",
+                             "Back-project a confocal or non-confocal capture (the optional field laserGridPositions) "
+                             "onto a voxel grid (volume, front view, depth).")
     ap.add_argument("--resolution", type=int, default=128)
-    ap.add_argument("--start", type=int, required=True, help="first time bin")
-    ap.add_argument("--end", type=int, required=True, help="one past the last time bin")
     ap.add_argument("--power", type=int, default=0, choices=range(5), help="weight d^power")
     ap.add_argument("--filter", choices=FILTERS, default="log")
     ap.add_argument("--sigma-bins", type=float, default=2.0)
-    ap.add_argument("--out", default="bp.npz")
-    ap.add_argument("--mesh", default=None, help="also write the isosurface as a PLY file")
-    ap.add_argument("--level-frac", type=float, default=0.5, help="isosurface level as a fraction of the maximum")
-    a = ap.parse_args(argv)
-    if a.end <= a.start:
-        ap.error("--end must be greater than --start")
-    return a
+    return _cli.parse(ap, argv)
 
 
 def main(argv=None):
     a = parse_args(argv)
-    from .data import make_data_kwargs
-    if not torch.cuda.is_available():
-        raise RuntimeError("nlosgr: backproject needs a GPU (no CPU fallback)")
-    dev = torch.device("cuda:0")
-    dk, *_ = make_data_kwargs(a.capture, dev, shuffle=False)
+    dk = _cli.open_capture(a.capture, "backproject")
     out = backproject_capture(dk, a.resolution, a.start, a.end, power=a.power, filter=a.filter, sigma_bins=a.sigma_bins)
-    grid, vol = out["grid"], out["volume"]
-    vp = dk["volume_position"].cpu().numpy().astype(np.float32)
-    # the key names of python -m nlosgr.voxelize (density / albedo both hold the volume; cam as its default)
-    np.savez_compressed(a.out, density=vol.cpu().numpy(), albedo=vol.cpu().numpy(), front=out["front"].cpu().numpy(),
-                        depth=out["depth"].cpu().numpy(), xs=grid.xs.numpy(), ys=grid.ys.numpy(), zs=grid.zs.numpy(),
-                        cam=np.array([vp[0], 0.0, vp[2]], dtype=np.float32))
-    print(f"wrote {a.out}: {grid.shape} voxels, {dk['camera_grid_positions'].shape[1]} wall points, bins "
-          f"[{a.start}, {a.end}), filter {a.filter}, power {a.power}")
-    if a.mesh:
-        from .mesh import isosurface, write_ply
-        level = a.level_frac * float(vol.max())
-        mesh = isosurface(vol, grid, level)
-        write_ply(a.mesh, mesh)
-        print(f"wrote {a.mesh}: level {level:.6g}, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles")
+    _cli.write_volume(a, dk, out, f"filter {a.filter}, power {a.power}")
 
 
 if __name__ == "__main__":

@@ -19,13 +19,12 @@ units: bin j of a row holds the light whose whole path is 2 (r0 + j c deltaT).
     python -m nlosgr.forward_project CAPTURE.mat --resolution R --start S --end E [--power P] [--iterations N]
         --out lw.npz [--mesh lw.ply --level-frac F]
 """
-import argparse
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _cli, _lib
 from .backproject import _gpu_f32, _lasers_arg, backproject, capture_lasers, fp32_window
 from .voxelize import VoxelGrid, front_view
 
@@ -243,22 +242,14 @@ def landweber_capture(data_kwargs, resolution, start, end, power=0, iterations=3
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m nlosgr.forward_project",
-                                 description="Least-squares voxel volume of a confocal or non-confocal capture (the "
-                                             "optional field laserGridPositions): Landweber iteration with the "
-                                             "forward projector and the back-projection.")
-    ap.add_argument("capture", help="Zaragoza-format .mat file")
+    ap = _cli.capture_parser("python -m nlosgr.forward_project", "lw.npz",
+                             "Least-squares voxel volume of a confocal or non-confocal capture (the optional field "
+                             "laserGridPositions): Landweber iteration with the forward projector and the "
+                             "back-projection.")
     ap.add_argument("--resolution", type=int, default=64)
-    ap.add_argument("--start", type=int, required=True, help="first time bin")
-    ap.add_argument("--end", type=int, required=True, help="one past the last time bin")
     ap.add_argument("--power", type=int, default=0, choices=range(5), help="weight d^power of the operator")
     ap.add_argument("--iterations", type=int, default=30)
-    ap.add_argument("--out", default="lw.npz")
-    ap.add_argument("--mesh", default=None, help="also write the isosurface as a PLY file")
-    ap.add_argument("--level-frac", type=float, default=0.5, help="isosurface level as a fraction of the maximum")
-    a = ap.parse_args(argv)
-    if a.end <= a.start:
-        ap.error("--end must be greater than --start")
+    a = _cli.parse(ap, argv)
     if a.iterations < 1:
         ap.error("--iterations must be >= 1")
     if a.resolution < 2:
@@ -268,27 +259,11 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
-    from .data import make_data_kwargs
-    if not torch.cuda.is_available():
-        raise RuntimeError("nlosgr: forward_project needs a GPU (no CPU fallback)")
-    dev = torch.device("cuda:0")
-    dk, *_ = make_data_kwargs(a.capture, dev, shuffle=False)
+    dk = _cli.open_capture(a.capture, "forward_project")
     out = landweber_capture(dk, a.resolution, a.start, a.end, power=a.power, iterations=a.iterations)
-    grid, vol = out["grid"], out["volume"]
     obj = out["objective"].cpu().numpy()
-    vp = dk["volume_position"].cpu().numpy().astype(np.float32)
-    # the key names of python -m nlosgr.backproject, plus the objective per iteration
-    np.savez_compressed(a.out, density=vol.cpu().numpy(), albedo=vol.cpu().numpy(), front=out["front"].cpu().numpy(),
-                        depth=out["depth"].cpu().numpy(), xs=grid.xs.numpy(), ys=grid.ys.numpy(), zs=grid.zs.numpy(),
-                        cam=np.array([vp[0], 0.0, vp[2]], dtype=np.float32), objective=obj)
-    print(f"wrote {a.out}: {grid.shape} voxels, {dk['camera_grid_positions'].shape[1]} wall points, bins "
-          f"[{a.start}, {a.end}), power {a.power}, {a.iterations} iterations, objective {obj[0]:.6g} -> {obj[-1]:.6g}")
-    if a.mesh:
-        from .mesh import isosurface, write_ply
-        level = a.level_frac * float(vol.max())
-        mesh = isosurface(vol, grid, level)
-        write_ply(a.mesh, mesh)
-        print(f"wrote {a.mesh}: level {level:.6g}, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles")
+    _cli.write_volume(a, dk, out, f"power {a.power}, {a.iterations} iterations, objective {obj[0]:.6g} -> {obj[-1]:.6g}",
+                      objective=obj)
 
 
 if __name__ == "__main__":

@@ -44,22 +44,16 @@ No CPU fallback.
     python -m nlosgr.lct CAPTURE.mat --start S --end E [--power P] [--snr X] [--nv N] [--backprop] --out lct.npz
         [--mesh lct.ply --level-frac F] [--iterations N [--no-accelerate] [--falloff Q]]
 """
-import argparse
 import functools
 
 import numpy as np
 import torch
 
-from . import _lib
-from .fk import X_ALONG, _extents, _gpu, _inside, _work, fk_grid, lattice_spacing, wall_lattice
-from .voxelize import front_view
+from . import _cli, _lib
+from .lattice import _extents, _f32, _gpu, _work, capture_result, confocal_lattice, fk_grid, lattice_rows
 
 MAX_CELLS = 2048
 MODE_WIENER, MODE_BACKPROP, MODE_GIVEN = 0, 1, 2
-
-
-def _f32(v):
-    return float(np.float32(v))
 
 
 def _cells(nv, nr):
@@ -167,26 +161,13 @@ def _load(symbol, what, rows, H, W, r0, dr, power, nv, perm, x_along, resampling
         raise ValueError(f"nlosgr: rows must be [{H * W}, nr] for an {H} x {W} lattice")
     res = _resampling(resampling, r0, dr, nr, nv)
     dev = rows.device
-    perm, sm, sn = _lattice(perm, x_along, H, W, dev, what)
+    perm, sm, sn = lattice_rows(perm, x_along, H, W, dev, what)
     pad = _work(out, (2 * H, 2 * W, 2 * res.nv), dev, what)
     first, start, weight = res.on(dev)[:3]
     _lib.check(getattr(lib, symbol)(_lib.ptr(rows), _lib.ptr(perm), H, W, nr, res.nv, sm, sn, float(r0), float(dr),
                                     int(power), _lib.ptr(first), _lib.ptr(start), _lib.ptr(weight), res.nnz,
                                     _lib.ptr(pad), _lib.stream_handle(dev)))
     return pad
-
-
-def _lattice(perm, x_along, H, W, dev, what):
-    """(perm checked, stride_m, stride_n): how lattice point (m, n) finds its row."""
-    if x_along not in X_ALONG:
-        raise ValueError(f"nlosgr: x_along must be one of {X_ALONG}")
-    if perm is not None:
-        perm = _gpu(perm, torch.int32, f"{what} (perm)")
-        if perm.shape != (H * W,) or perm.device != dev:
-            raise ValueError(f"nlosgr: perm must be int32 [{H * W}] on {dev}")
-        if int(perm.min()) < 0 or int(perm.max()) >= H * W:
-            raise ValueError("nlosgr: perm holds a row index outside [0, H W)")
-    return (perm,) + ((W, 1) if x_along == "n" else (1, H))
 
 
 @torch.no_grad()
@@ -362,7 +343,7 @@ def lct_store_rows(field, resampling, power=0, perm=None, x_along="n", out=None)
     if not isinstance(resampling, Resampling) or resampling.nv != nv:
         raise ValueError(f"nlosgr: resampling must be lct_resampling's result with nv = {nv}")
     nr, dev = resampling.nr, field.device
-    perm, sm, sn = _lattice(perm, x_along, H, W, dev, "lct_store_rows")
+    perm, sm, sn = lattice_rows(perm, x_along, H, W, dev, "lct_store_rows")
     if out is None:
         rows = torch.empty((H * W, nr), dtype=torch.float32, device=dev)
     else:
@@ -403,7 +384,7 @@ class LctOperator:
         self.work = lct_kernel(self.H, self.W, self.nv, sx, sz, self.resampling.dv, device=device)
         self.device = self.work.device
         self.Fk = torch.fft.fftn(self.work)
-        self.perm, _, _ = _lattice(perm, x_along, self.H, self.W, self.device, "LctOperator")
+        self.perm, _, _ = lattice_rows(perm, x_along, self.H, self.W, self.device, "LctOperator")
         self.x_along = x_along
 
     @property
@@ -563,35 +544,6 @@ def lct_reconstruct(rows, H, W, sx, sz, r0, dr, power=4, snr=0.8, nv=None, backp
     return lct_store(torch.fft.ifftn(spec), res)
 
 
-def _capture_lattice(data_kwargs, start, end, what):
-    """(rows, H, W, xs, zs, y0, perm, x_along, sx, sz, r0, dr, nr) of a confocal capture on its wall lattice."""
-    from .data import is_confocal, volume_target
-    if not is_confocal(data_kwargs):
-        raise NotImplementedError(f"nlosgr: {what} is confocal only: this capture's laser spots "
-                                  "(laser_grid_positions) differ from its sensed points.  Use nlosgr.phasor (or "
-                                  "nlosgr.backproject), which take the laser spots")
-    I1 = int(np.floor(start))
-    nr = int(end - start)
-    H, W, xs, zs, y0, perm, x_along = wall_lattice(data_kwargs)
-    _extents(H, W, nr)
-    rows = volume_target(data_kwargs, start, nr)
-    cdt = float(data_kwargs["c"]) * float(data_kwargs["deltaT"])
-    sx = lattice_spacing(xs, None if len(xs) > 1 else lattice_spacing(zs))
-    sz = lattice_spacing(zs, sx)
-    return rows, H, W, xs, zs, y0, perm.to(rows.device), x_along, sx, sz, I1 * cdt, cdt, nr
-
-
-def _capture_result(vol, grid, data_kwargs, crop):
-    if crop:
-        vp = [float(v) for v in data_kwargs["volume_position"]]
-        h = float(data_kwargs["volume_size"]) / 2
-        rx, ry, rz = (_inside(t.numpy(), p - h, p + h) for t, p in zip(grid.tables, vp))
-        vol = vol[rx[0]:rx[1], ry[0]:ry[1], rz[0]:rz[1]].contiguous()
-        grid = grid.slice(rx, ry, rz)
-    front, depth = front_view(vol, grid)
-    return {"volume": vol, "front": front, "depth": depth, "grid": grid}
-
-
 @torch.no_grad()
 def lct_capture(data_kwargs, start, end, power=4, snr=0.8, nv=None, backprop=False, crop=True, inverse=None):
     """The light-cone transform of the capture in data_kwargs (data.make_data_kwargs, shuffled or not) over bins
@@ -599,11 +551,10 @@ def lct_capture(data_kwargs, start, end, power=4, snr=0.8, nv=None, backprop=Fal
     fk.fk_capture does.  Returns {"volume" [nx,ny,nz], "front", "depth" (voxelize.front_view), "grid"}, the keys of
     fk_capture.  A non-confocal capture raises NotImplementedError; a wall that is no lattice, wall_lattice's
     ValueError."""
-    rows, H, W, xs, zs, y0, perm, x_along, sx, sz, r0, dr, nr = _capture_lattice(data_kwargs, start, end,
-                                                                                 "the light-cone transform")
-    vol = lct_reconstruct(rows, H, W, sx, sz, r0, dr, power=power, snr=snr, nv=nv, backprop=backprop, perm=perm,
-                          x_along=x_along, inverse=inverse)
-    return _capture_result(vol, fk_grid(xs, zs, y0, r0, dr, nr), data_kwargs, crop)
+    c = confocal_lattice(data_kwargs, start, end, "the light-cone transform")
+    vol = lct_reconstruct(c.rows, c.H, c.W, c.sx, c.sz, c.r0, c.dr, power=power, snr=snr, nv=nv, backprop=backprop,
+                          perm=c.perm, x_along=c.x_along, inverse=inverse)
+    return capture_result(data_kwargs, fk_grid(c.xs, c.zs, c.y0, c.r0, c.dr, c.nr), vol, crop)
 
 
 @torch.no_grad()
@@ -618,26 +569,22 @@ def lct_solve_capture(data_kwargs, start, end, falloff=3, power=0, iterations=30
     (A at power -3 is the confocal transient), but at power -3 the operator carries r^-3 itself, and in a window
     that starts at r0 = 0 its first bins give it a norm of about 1e11: the step 1 / norm is then so small that the
     far voxels do not move and the solve stalls.  Moving the r^3 to the rows leaves an operator of norm about 1."""
-    rows, H, W, xs, zs, y0, perm, x_along, sx, sz, r0, dr, nr = _capture_lattice(data_kwargs, start, end,
-                                                                                 "the LCT solver")
-    rows = _gpu(rows.float(), torch.float32, "lct_solve_capture")
+    c = confocal_lattice(data_kwargs, start, end, "the LCT solver")
+    rows = _gpu(c.rows.float(), torch.float32, "lct_solve_capture")
     if falloff:
-        radii = r0 + dr * torch.arange(nr, dtype=torch.float64, device=rows.device)
+        radii = c.r0 + c.dr * torch.arange(c.nr, dtype=torch.float64, device=rows.device)
         rows = (rows.double() * radii.pow(float(falloff))[None]).float()
-    op = LctOperator(H, W, sx, sz, r0, dr, nr, power=power, nv=nv, perm=perm, x_along=x_along, device=rows.device)
+    op = LctOperator(c.H, c.W, c.sx, c.sz, c.r0, c.dr, c.nr, power=power, nv=nv, perm=c.perm, x_along=c.x_along,
+                     device=rows.device)
     vol, objective = lct_solve(rows, op, iterations=iterations, accelerate=accelerate)
-    out = _capture_result(vol, op.grid(xs, zs, y0), data_kwargs, crop)
+    out = capture_result(data_kwargs, op.grid(c.xs, c.zs, c.y0), vol, crop)
     out["objective"] = objective
     return out
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m nlosgr.lct",
-                                 description="Light-cone transform of a confocal capture on its own wall x time "
-                                             "lattice (volume, front view, depth).")
-    ap.add_argument("capture", help="Zaragoza-format .mat file")
-    ap.add_argument("--start", type=int, required=True, help="first time bin")
-    ap.add_argument("--end", type=int, required=True, help="one past the last time bin")
+    ap = _cli.capture_parser("python -m nlosgr.lct", "lct.npz", "Light-cone transform of a confocal capture on its own "
+                                                                "wall x time lattice (volume, front view, depth).")
     ap.add_argument("--power", type=int, default=None, choices=range(-4, 5),
                     help="falloff compensation r^power, 0..4 (default 4); with --iterations the operator's power, "
                          "-4..4 (default 0)")
@@ -650,12 +597,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-accelerate", dest="accelerate", action="store_false",
                     help="with --iterations: plain Landweber steps instead of FISTA")
     ap.add_argument("--falloff", type=float, default=3.0, help="with --iterations: multiply bin j by (r0 + j dr)^falloff")
-    ap.add_argument("--out", default="lct.npz")
-    ap.add_argument("--mesh", default=None, help="also write the isosurface as a PLY file")
-    ap.add_argument("--level-frac", type=float, default=0.5, help="isosurface level as a fraction of the maximum")
-    a = ap.parse_args(argv)
-    if a.end <= a.start:
-        ap.error("--end must be greater than --start")
+    a = _cli.parse(ap, argv)
     if a.iterations < 0:
         ap.error("--iterations must be >= 0")
     if a.power is None:
@@ -671,11 +613,7 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
-    from .data import make_data_kwargs
-    if not torch.cuda.is_available():
-        raise RuntimeError("nlosgr: the light-cone transform needs a GPU (no CPU fallback)")
-    dev = torch.device("cuda:0")
-    dk, *_ = make_data_kwargs(a.capture, dev, shuffle=False)
+    dk = _cli.open_capture(a.capture, "the light-cone transform")
     if a.iterations:
         out = lct_solve_capture(dk, a.start, a.end, falloff=a.falloff, power=a.power, iterations=a.iterations,
                                 accelerate=a.accelerate, nv=a.nv)
@@ -685,20 +623,7 @@ def main(argv=None):
         out = lct_capture(dk, a.start, a.end, power=a.power, snr=a.snr, nv=a.nv, backprop=a.backprop)
         extra = {}
         how = "back-projection" if a.backprop else f"snr {a.snr:g}"
-    grid, vol = out["grid"], out["volume"]
-    vp = dk["volume_position"].cpu().numpy().astype(np.float32)
-    # the key names of python -m nlosgr.fk
-    np.savez_compressed(a.out, density=vol.cpu().numpy(), albedo=vol.cpu().numpy(), front=out["front"].cpu().numpy(),
-                        depth=out["depth"].cpu().numpy(), xs=grid.xs.numpy(), ys=grid.ys.numpy(), zs=grid.zs.numpy(),
-                        cam=np.array([vp[0], 0.0, vp[2]], dtype=np.float32), **extra)
-    print(f"wrote {a.out}: {grid.shape} voxels, {dk['camera_grid_positions'].shape[1]} wall points, bins "
-          f"[{a.start}, {a.end}), power {a.power}, {how}")
-    if a.mesh:
-        from .mesh import isosurface, write_ply
-        level = a.level_frac * float(vol.max())
-        mesh = isosurface(vol, grid, level)
-        write_ply(a.mesh, mesh)
-        print(f"wrote {a.mesh}: level {level:.6g}, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles")
+    _cli.write_volume(a, dk, out, f"power {a.power}, {how}", **extra)
 
 
 if __name__ == "__main__":

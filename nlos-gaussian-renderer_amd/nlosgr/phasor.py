@@ -19,14 +19,13 @@ No CPU fallback, no backward.
     python -m nlosgr.phasor CAPTURE.mat --resolution 128 --start S --end E --wavelength L [--cycles C]
         [--power P] --out ph.npz [--mesh ph.ply --level-frac F]
 """
-import argparse
 import ctypes
 import math
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _cli, _lib
 from .backproject import _gpu_f32, _lasers_arg, capture_lasers, fp32_window
 from .irf import IRF, MAX_TAPS, irf_apply
 from .voxelize import VoxelGrid, front_view
@@ -137,49 +136,24 @@ def phasor_capture(data_kwargs, resolution, start, end, wavelength, cycles=4.0, 
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m nlosgr.phasor",
-                                 description="Phasor-field reconstruction of a confocal or non-confocal capture (the "
-                                             "optional field laserGridPositions) on a voxel grid.")
-    ap.add_argument("capture", help="Zaragoza-format .mat file")
+    ap = _cli.capture_parser("python -m nlosgr.phasor", "ph.npz",
+                             "Phasor-field reconstruction of a confocal or non-confocal capture (the optional field "
+                             "laserGridPositions) on a voxel grid.")
     ap.add_argument("--resolution", type=int, default=128)
-    ap.add_argument("--start", type=int, required=True, help="first time bin")
-    ap.add_argument("--end", type=int, required=True, help="one past the last time bin")
     ap.add_argument("--wavelength", type=float, required=True,
                     help="virtual wavelength in scene units along the whole path (2-4 wall-point spacings or more)")
     ap.add_argument("--cycles", type=float, default=4.0, help="periods inside +-3 sigma of the envelope")
     ap.add_argument("--power", type=int, default=0, choices=range(5), help="weight d^power")
-    ap.add_argument("--out", default="ph.npz")
-    ap.add_argument("--mesh", default=None, help="also write the isosurface as a PLY file")
-    ap.add_argument("--level-frac", type=float, default=0.5, help="isosurface level as a fraction of the maximum")
-    a = ap.parse_args(argv)
-    if a.end <= a.start:
-        ap.error("--end must be greater than --start")
-    return a
+    return _cli.parse(ap, argv)
 
 
 def main(argv=None):
     a = parse_args(argv)
-    from .data import make_data_kwargs
-    if not torch.cuda.is_available():
-        raise RuntimeError("nlosgr: phasor needs a GPU (no CPU fallback)")
-    dev = torch.device("cuda:0")
-    dk, *_ = make_data_kwargs(a.capture, dev, shuffle=False)
+    dk = _cli.open_capture(a.capture, "phasor")
     out = phasor_capture(dk, a.resolution, a.start, a.end, a.wavelength, cycles=a.cycles, power=a.power)
-    grid, vol = out["grid"], out["volume"]
-    vp = dk["volume_position"].cpu().numpy().astype(np.float32)
     # the key names of python -m nlosgr.backproject (density / albedo both hold the magnitude), plus the planes
-    np.savez_compressed(a.out, density=vol.cpu().numpy(), albedo=vol.cpu().numpy(), front=out["front"].cpu().numpy(),
-                        depth=out["depth"].cpu().numpy(), xs=grid.xs.numpy(), ys=grid.ys.numpy(), zs=grid.zs.numpy(),
-                        cam=np.array([vp[0], 0.0, vp[2]], dtype=np.float32), real=out["real"].cpu().numpy(),
-                        imag=out["imag"].cpu().numpy())
-    print(f"wrote {a.out}: {grid.shape} voxels, {dk['camera_grid_positions'].shape[1]} wall points, bins "
-          f"[{a.start}, {a.end}), wavelength {a.wavelength}, cycles {a.cycles}, power {a.power}")
-    if a.mesh:
-        from .mesh import isosurface, write_ply
-        level = a.level_frac * float(vol.max())
-        mesh = isosurface(vol, grid, level)
-        write_ply(a.mesh, mesh)
-        print(f"wrote {a.mesh}: level {level:.6g}, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles")
+    _cli.write_volume(a, dk, out, f"wavelength {a.wavelength}, cycles {a.cycles}, power {a.power}",
+                      real=out["real"].cpu().numpy(), imag=out["imag"].cpu().numpy())
 
 
 if __name__ == "__main__":

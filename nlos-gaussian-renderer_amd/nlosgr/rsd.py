@@ -24,22 +24,17 @@ No CPU fallback, no backward.
     python -m nlosgr.rsd CAPTURE.mat --resolution R --start S --end E --wavelength L [--cycles C] [--power P]
         --out rsd.npz [--mesh rsd.ply --level-frac F]
 """
-import argparse
 import math
 
 import numpy as np
 import torch
 
-from . import _lib
-from .fk import X_ALONG, _gpu, _inside, _work, lattice_spacing, wall_lattice
-from .voxelize import MAX_EXTENT, VoxelGrid, front_view
+from . import _cli, _lib
+from .lattice import _f32, _gpu, _work, capture_lattice, capture_result, lattice_rows, lattice_spacing
+from .voxelize import MAX_EXTENT, VoxelGrid
 
 MAX_NT = 8192
 MAX_BAND = 512
-
-
-def _f32(v):
-    return float(np.float32(v))
 
 
 def rsd_band(wavelength, dr, Nt, r0, cycles=4.0):
@@ -157,21 +152,13 @@ def rsd_load(spec, H, W, q_lo, coef, perm=None, x_along="n", out=None):
     H, W = _lattice(H, W)
     if spec.dim() != 2 or spec.shape[0] != H * W or spec.shape[1] < 2:
         raise ValueError(f"nlosgr: rsd_load takes a spectrum [{H * W}, Nt/2 + 1] for an {H} x {W} lattice")
-    if x_along not in X_ALONG:
-        raise ValueError(f"nlosgr: x_along must be one of {X_ALONG}")
     dev = spec.device
     Nt = 2 * (int(spec.shape[1]) - 1)
     coef = torch.as_tensor(coef).to(device=dev, dtype=torch.complex64).reshape(-1).contiguous()
     nq, q_lo = int(coef.shape[0]), int(q_lo)
     if not (1 <= nq <= MAX_BAND and q_lo >= 1 and q_lo + nq - 1 <= Nt // 2 - 1):
         raise ValueError(f"nlosgr: the band [q_lo, q_lo + nq) must lie in [1, Nt/2 - 1] and hold 1..{MAX_BAND} bins")
-    if perm is not None:
-        perm = _gpu(perm, torch.int32, "rsd_load (perm)")
-        if perm.shape != (H * W,) or perm.device != dev:
-            raise ValueError(f"nlosgr: perm must be int32 [{H * W}] on {dev}")
-        if int(perm.min()) < 0 or int(perm.max()) >= H * W:
-            raise ValueError("nlosgr: perm holds a row index outside [0, H W)")
-    sm, sn = (W, 1) if x_along == "n" else (1, H)
+    perm, sm, sn = lattice_rows(perm, x_along, H, W, dev, "rsd_load")
     pw = _work(out, (nq, 2 * H, 2 * W), dev, "rsd_load")
     _lib.check(lib.nlosgr_rsd_load(_lib.ptr(spec), _lib.ptr(perm), _lib.ptr(coef), H, W, Nt, q_lo, nq, sm, sn,
                                    _lib.ptr(pw), _lib.stream_handle(dev)))
@@ -335,78 +322,39 @@ def capture_laser(data_kwargs):
 @torch.no_grad()
 def rsd_capture(data_kwargs, resolution, start, end, wavelength, cycles=4.0, power=0, crop=True):
     """Fast phasor-field image of the capture in data_kwargs (data.make_data_kwargs, shuffled or not) over bins
-    [floor(start), floor(start) + end - start): x and z are the wall lattice's own (fk.wall_lattice), the depths are
+    [floor(start), floor(start) + end - start): x and z are the wall lattice's own (lattice.wall_lattice), the depths
     the y table of VoxelGrid(volume_position, volume_size, resolution), as phasor_capture's.  crop: keep the lattice
     points inside the capture's volume box, a contiguous block, as fk_capture does.  A capture with one laser spot (a
     [3, 1] field, or all spots equal) is reconstructed with it; distinct spots raise NotImplementedError.  Returns
     the keys of phasor_capture: {"volume" (the magnitude), "real", "imag", "front", "depth", "grid"}."""
-    from .data import volume_target
     laser = capture_laser(data_kwargs)
-    I1 = int(np.floor(start))
-    nr = int(end - start)
-    H, W, xs, zs, y0, perm, x_along = wall_lattice(data_kwargs)
-    rows = volume_target(data_kwargs, start, nr)
-    cdt = float(data_kwargs["c"]) * float(data_kwargs["deltaT"])
+    c = capture_lattice(data_kwargs, start, end, extents=False)
     vp = [float(v) for v in data_kwargs["volume_position"]]
     ys = VoxelGrid(vp, float(data_kwargs["volume_size"]), resolution).ys
-    planes, mag = rsd_reconstruct(rows, H, W, xs, zs, y0, ys, I1 * cdt, cdt, wavelength, cycles=cycles, power=power,
-                                  laser=laser, perm=perm.to(rows.device), x_along=x_along)
-    grid = VoxelGrid(tables=(xs, ys, zs))
-    if crop:
-        h = float(data_kwargs["volume_size"]) / 2
-        rx, rz = (_inside(t.numpy(), p - h, p + h) for t, p in ((xs, vp[0]), (zs, vp[2])))
-        planes = planes[:, rx[0]:rx[1], :, rz[0]:rz[1]].contiguous()
-        mag = mag[rx[0]:rx[1], :, rz[0]:rz[1]].contiguous()
-        grid = grid.slice(rx, None, rz)
-    front, depth = front_view(mag, grid)
-    return {"volume": mag, "real": planes[0], "imag": planes[1], "front": front, "depth": depth, "grid": grid}
+    planes, mag = rsd_reconstruct(c.rows, c.H, c.W, c.xs, c.zs, c.y0, ys, c.r0, c.dr, wavelength, cycles=cycles,
+                                  power=power, laser=laser, perm=c.perm, x_along=c.x_along)
+    return capture_result(data_kwargs, VoxelGrid(tables=(c.xs, ys, c.zs)), mag, crop, axes=(0, 2), real=planes[0],
+                          imag=planes[1])
 
 
 def parse_args(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m nlosgr.rsd",
-                                 description="Fast phasor-field reconstruction (Rayleigh-Sommerfeld diffraction by FFT) "
-                                             "of a confocal capture or one with a single laser spot, on the wall's "
-                                             "lattice x the volume's depths.")
-    ap.add_argument("capture", help="Zaragoza-format .mat file")
+    ap = _cli.capture_parser("python -m nlosgr.rsd", "rsd.npz",
+                             "Fast phasor-field reconstruction (Rayleigh-Sommerfeld diffraction by FFT) of a confocal "
+                             "capture or one with a single laser spot, on the wall's lattice x the volume's depths.")
     ap.add_argument("--resolution", type=int, default=128, help="depth planes across the volume box")
-    ap.add_argument("--start", type=int, required=True, help="first time bin")
-    ap.add_argument("--end", type=int, required=True, help="one past the last time bin")
     ap.add_argument("--wavelength", type=float, required=True,
                     help="virtual wavelength in scene units along the whole path (2-4 wall-point spacings or more)")
     ap.add_argument("--cycles", type=float, default=4.0, help="periods inside +-3 sigma of the envelope")
     ap.add_argument("--power", type=int, default=0, choices=range(5), help="weight d^power")
-    ap.add_argument("--out", default="rsd.npz")
-    ap.add_argument("--mesh", default=None, help="also write the isosurface as a PLY file")
-    ap.add_argument("--level-frac", type=float, default=0.5, help="isosurface level as a fraction of the maximum")
-    a = ap.parse_args(argv)
-    if a.end <= a.start:
-        ap.error("--end must be greater than --start")
-    return a
+    return _cli.parse(ap, argv)
 
 
 def main(argv=None):
     a = parse_args(argv)
-    from .data import make_data_kwargs
-    if not torch.cuda.is_available():
-        raise RuntimeError("nlosgr: the fast phasor field needs a GPU (no CPU fallback)")
-    dev = torch.device("cuda:0")
-    dk, *_ = make_data_kwargs(a.capture, dev, shuffle=False)
+    dk = _cli.open_capture(a.capture, "the fast phasor field")
     out = rsd_capture(dk, a.resolution, a.start, a.end, a.wavelength, cycles=a.cycles, power=a.power)
-    grid, vol = out["grid"], out["volume"]
-    vp = dk["volume_position"].cpu().numpy().astype(np.float32)
-    # the key names of python -m nlosgr.phasor
-    np.savez_compressed(a.out, density=vol.cpu().numpy(), albedo=vol.cpu().numpy(), front=out["front"].cpu().numpy(),
-                        depth=out["depth"].cpu().numpy(), xs=grid.xs.numpy(), ys=grid.ys.numpy(), zs=grid.zs.numpy(),
-                        cam=np.array([vp[0], 0.0, vp[2]], dtype=np.float32), real=out["real"].cpu().numpy(),
-                        imag=out["imag"].cpu().numpy())
-    print(f"wrote {a.out}: {grid.shape} voxels, {dk['camera_grid_positions'].shape[1]} wall points, bins "
-          f"[{a.start}, {a.end}), wavelength {a.wavelength}, cycles {a.cycles}, power {a.power}")
-    if a.mesh:
-        from .mesh import isosurface, write_ply
-        level = a.level_frac * float(vol.max())
-        mesh = isosurface(vol, grid, level)
-        write_ply(a.mesh, mesh)
-        print(f"wrote {a.mesh}: level {level:.6g}, {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} triangles")
+    _cli.write_volume(a, dk, out, f"wavelength {a.wavelength}, cycles {a.cycles}, power {a.power}",
+                      real=out["real"].cpu().numpy(), imag=out["imag"].cpu().numpy())
 
 
 if __name__ == "__main__":

@@ -182,18 +182,19 @@ def fit_capture(data_kwargs, model, resolution, start, end, power=0, falloff=0, 
     if projector not in ("exact", "lct"):
         raise ValueError("nlosgr: projector must be 'exact' or 'lct'")
     if projector == "lct":
-        from .lct import LctOperator, _capture_lattice
-        rows, H, W, xs, zs, y0, perm, x_along, sx, sz, r0, cdt, nr = _capture_lattice(data_kwargs, start, end,
-                                                                                      "the LCT projector")
-        rows = _gpu_f32(rows.float(), "fit_capture")
+        from .lattice import confocal_lattice
+        from .lct import LctOperator
+        c = confocal_lattice(data_kwargs, start, end, "the LCT projector")
+        rows = _gpu_f32(c.rows.float(), "fit_capture")
         if falloff:
-            radii = r0 + cdt * torch.arange(nr, dtype=torch.float64, device=rows.device)
+            radii = c.r0 + c.dr * torch.arange(c.nr, dtype=torch.float64, device=rows.device)
             rows = (rows.double() * radii.pow(float(falloff))[None]).float()
-        op = LctOperator(H, W, sx, sz, r0, cdt, nr, power=power, nv=nv, perm=perm, x_along=x_along, device=rows.device)
+        op = LctOperator(c.H, c.W, c.sx, c.sz, c.r0, c.dr, c.nr, power=power, nv=nv, perm=c.perm, x_along=c.x_along,
+                         device=rows.device)
         if cam is None:
             cam = (float(data_kwargs["volume_position"][0]), 0.0, float(data_kwargs["volume_position"][2]))
         kw.setdefault("irf", data_kwargs.get("irf"))
-        return VoxelFitStep(model, op.grid(xs, zs, y0), cam, rows=rows, operator=op, **kw)
+        return VoxelFitStep(model, op.grid(c.xs, c.zs, c.y0), cam, rows=rows, operator=op, **kw)
     from .data import volume_target
     I1 = int(np.floor(start))
     nr = int(end - start)
