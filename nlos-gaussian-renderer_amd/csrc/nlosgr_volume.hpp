@@ -344,7 +344,8 @@ constexpr int kStepsNetf = NLOSGR_FSTEPS_NETF;
 // the twin drain (fx_twin_setup) runs longer rounds: a round costs two sets of exp2 seeds, and its unions are
 // longer than single segments (one GPU, 24 / 28 / 32 bins: fwd 657.6 / 642.2 / 632.5 ms; another, 32 / 36 / 40 /
 // 48 bins: 635.7 / 625.1 / 623.7 / 623.6 ms; with run-following pairs, 36 / 40 / 44 bins: 564.5 / 562.0 / 563.0 ms,
-// and on another GPU 36 / 40: 566.3 / 564.6 ms: within 2.5 ms of each other, so 36 stays)
+// and on another GPU 36 / 40: 566.3 / 564.6 ms: within 2.5 ms of each other, so 36 stays; with the tail refill rule
+// and no placement, 32 / 36 / 40 bins: 507.1 / 504.8 / 507.6 ms)
 #ifndef NLOSGR_FSTEPS_TWIN
 #define NLOSGR_FSTEPS_TWIN 36
 #endif

@@ -56,7 +56,9 @@ constexpr int kRefill = NLOSGR_REFILL;     // refill once this many lanes are id
 #ifndef NLOSGR_REFILL_FX
 #define NLOSGR_REFILL_FX 56
 #endif
-constexpr int kRefillFx = NLOSGR_REFILL_FX;   // the no-occlusion FX drain with the refill deal
+// the no-occlusion FX drain with the refill deal (the twin drain without placement, 44 / 48 / 52 / 56 / 60 idle
+// lanes: fwd 502.4 / 501.1 / 502.6 / 504.8 / 511.4 ms, one GPU: within 4 ms, so 56 stays)
+constexpr int kRefillFx = NLOSGR_REFILL_FX;
 
 #ifndef NLOSGR_FXPERM
 #define NLOSGR_FXPERM 1   // FX refill permutation (the deal, see fx_perm): with the bank placement 745.7 vs 750.6 ms
@@ -215,7 +217,7 @@ constexpr float kBetaSeries = 0.5f;   // bin-integrated TAIL drain: series bin a
 // waves' fields to the global u64 histogram [P][nr] (all Gaussian splits of a wall point meet there), and
 // fx_reduce_kernel scales it to floats.
 #ifdef NLOSGR_FXCOUNT
-__device__ unsigned long long g_fdbg[8];
+__device__ unsigned long long g_fdbg[12];
 #endif
 constexpr int kFxBits = 24;
 constexpr int kFxRange = 16;                 // E <= E(max bound) + kFxRange: u64 terms < 2^(kFxBits + kFxRange)
@@ -287,9 +289,9 @@ __device__ __forceinline__ void fx_gadd(unsigned long long* at, float v) {
 
 // a lane without a second ray: al2 = kNoTwin makes every value of the second recurrence exp2(-200) = 0
 constexpr float kNoTwin = -200.f;
-// FX refill placement (see kFxShift): newl = this lane took a new segment, act = it holds one
-// (TW: a lane's twin moves both rays, so its reach is the shorter of the two)
-template <bool TW = false>
+// FX refill placement (see kFxShift): newl = this lane took a new segment, act = it holds one.  Not for the twin
+// drain: with two rays per lane its shifts and their extra bins cost more than the conflicts they avoid
+// (rejected table)
 __device__ __forceinline__ void fx_place(bool newl, bool act, Drain& d) {
     if (!__builtin_amdgcn_ballot_w64(newl)) return;
     const int pb = d.pos >> 1, ph = pb & 15, o = d.pos & 1;
@@ -297,12 +299,7 @@ __device__ __forceinline__ void fx_place(bool newl, bool act, Drain& d) {
     // reach: the seed exponent at the new start stays >= -100 (no flush to zero), the start >= bin 0
     const float span = d.al + 100.f;
     const float tm = span > 0.f ? __builtin_amdgcn_sqrtf(span * __builtin_amdgcn_rcpf(fmaxf(-d.ga, 1e-30f))) : 0.f;
-    int smax = newl ? min(min(kFxShift, pb), (int)floorf(0.5f * (d.t - (float)o + tm))) : -1;
-    if (TW && d.al2 > kNoTwin) {
-        const float span2 = d.al2 + 100.f;
-        const float tm2 = span2 > 0.f ? __builtin_amdgcn_sqrtf(span2 * __builtin_amdgcn_rcpf(fmaxf(-d.ga2, 1e-30f))) : 0.f;
-        smax = min(smax, (int)floorf(0.5f * (d.t2 - (float)o + tm2)));
-    }
+    const int smax = newl ? min(min(kFxShift, pb), (int)floorf(0.5f * (d.t - (float)o + tm))) : -1;
     bool pend = newl && smax >= 0;
     int sh = 0;
 #pragma unroll
@@ -323,7 +320,6 @@ __device__ __forceinline__ void fx_place(bool newl, bool act, Drain& d) {
         d.pos -= delta;
         d.rem += delta;
         d.t -= (float)delta;
-        if (TW) d.t2 -= (float)delta;
     }
 }
 
@@ -353,6 +349,24 @@ __device__ __forceinline__ void fx_perm(bool& newl, bool& act, Drain& d, float& 
     const int s = __popcll(lt) + lanes_below(eq);
     const int dst = ((s & 3) << 4) | (s >> 2);
     const int a4 = dst << 2;
+    if (TW) {
+        // one word carries rem, pos and the two flags: an active lane has 0 < rem and 0 <= pos < pos + rem <= nr,
+        // nr <= 4096 (validate), so 13 bits hold each.  The peak sum fpk is not moved: the headroom re-arm, the
+        // only reader of a dealt segment's peak, computes it again from al and al2
+        const int ri = act ? (d.rem | (d.pos << 13) | (newl ? (1 << 30) : 0)) : 0;
+        const int ri2 = __builtin_amdgcn_ds_permute(a4, ri);
+        d.t = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.t)));
+        d.ga = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.ga)));
+        d.al = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.al)));
+        d.t2 = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.t2)));
+        d.ga2 = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.ga2)));
+        d.al2 = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.al2)));
+        act = ri2 != 0;
+        newl = (ri2 >> 30) & 1;
+        d.rem = ri2 & 0x1FFF;
+        d.pos = (ri2 >> 13) & 0x1FFF;
+        return;
+    }
     const int ri = act ? (d.rem | (newl ? (1 << 30) : 0)) : 0;
     const int ri2 = __builtin_amdgcn_ds_permute(a4, ri);
     d.pos = __builtin_amdgcn_ds_permute(a4, d.pos);
@@ -363,11 +377,6 @@ __device__ __forceinline__ void fx_perm(bool& newl, bool& act, Drain& d, float& 
     if (MODE == NLOSGR_MODE_NETF) {   // the segment's transmittance (carrying its weight) and sigma c dT
         d.T = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.T)));
         d.sc = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.sc)));
-    }
-    if (TW) {   // the lane's second ray
-        d.t2 = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.t2)));
-        d.ga2 = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.ga2)));
-        d.al2 = __int_as_float(__builtin_amdgcn_ds_permute(a4, __float_as_int(d.al2)));
     }
     act = ri2 != 0;
     newl = (ri2 >> 30) & 1;
@@ -493,7 +502,8 @@ __device__ __forceinline__ void tail_round(const Drain& d, const float t, float&
     }
 }
 
-// Twin drain (TW; the no-occlusion FX forward with the refill deal, the training hot path).  The forward is
+// Twin drain (TW; the no-occlusion FX forward with the refill deal and without the bank placement, the training
+// hot path).  The forward is
 // paced by the number of ds_add_u64 it issues, and that number is set by rays: a lane that drains the two
 // adjacent cells (i, j), (i, j + 1) of one pair at once sums their values in registers and issues one add for
 // both (the cells are paired along their row's run of passing cells, see enumerate_runs).
@@ -634,7 +644,9 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
     unsigned long long nsamp = 0;
 
 #ifdef NLOSGR_FXCOUNT
-    unsigned long long fdbg[5] = {0ull, 0ull, 0ull, 0ull, 0ull};   // wave-uniform diagnostics
+    unsigned long long fdbg[9] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};   // wave-uniform diagnostics
+    // ([0..4]: the rounds' bank-pair occupancy; [5..8]: refills, entries taken, refills taking < 32 entries,
+    // refills after the chunk's enumeration ended)
 #endif
     Drain d;
     d.pos = 0; d.rem = 0; d.t = 0.f; d.ga = 0.f; d.al = 0.f; d.st = 0.f;
@@ -698,7 +710,18 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
             // the no-occlusion FX drain refills later: the deal's cost is per refill (REFILL 48 / 52 / 56 / 60 / 62:
             // 745.9 / 735.7 / 732.4 / 736.7 / 745.4 ms, same box)
             constexpr int kRef = (FX && !BR && kFxPerm && MODE == NLOSGR_MODE_NOOCL) ? kRefillFx : kRefill;
-            if (qcount > 0 && (nidle >= kRef || !anymore)) {
+            // TW, the chunk's tail (every box exhausted): a refill waits until it can take the whole queue or kRef
+            // entries, since a refill costs about one drain round whatever it takes (C3: 7.5 % fewer refills for
+            // 0.4 % more rounds).  It ends: no lane enumerates, so active lanes only finish and nidle reaches
+            // 64 >= min(kRef, qcount); scripts/refill_replay.py replays the loop on the CPU
+            const bool refill = TW ? nidle >= (anymore ? kRef : min(kRef, qcount)) : (nidle >= kRef || !anymore);
+            if (qcount > 0 && refill) {
+#ifdef NLOSGR_FXCOUNT
+                if (FX && !BR) {
+                    const unsigned long long nt_ = (unsigned long long)min(nidle, qcount);
+                    fdbg[5] += 1ull; fdbg[6] += nt_; fdbg[7] += nt_ < 32ull ? 1ull : 0ull; fdbg[8] += anymore ? 0ull : 1ull;
+                }
+#endif
                 // idle lane of rank r takes queue entry qhead + r; pair data come from lane `slot`
                 const int r = lanes_below(idle);
                 const bool take = !act && r < qcount;
@@ -766,7 +789,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                 // netf has neither the deal (measured slower: its drain is less LDS-bound) nor the refill
                 // placement (its transmittance would need re-seeding)
                 if (FX && !BR && kFxPerm && MODE == NLOSGR_MODE_NOOCL) fx_perm<MODE, TW>(newl, act, d, fpk);
-                if (FX && !BR && kFxShift > 0 && MODE != NLOSGR_MODE_NETF) fx_place<TW>(newl, act, d);
+                if (FX && !BR && !TW && kFxShift > 0 && MODE != NLOSGR_MODE_NETF) fx_place(newl, act, d);
             }
             const bool anyact = __builtin_amdgcn_ballot_w64(act) != 0;
             if (!anyact) {
@@ -797,7 +820,11 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                     mx = 0u;
                 }
                 fthr = (kFxLimit - (float)mx) * (1.0f / 64.0f);
-                fxs = act ? fpk : 0.f;   // an active segment may still add up to its peak to any bin
+                // an active segment may still add up to its peak to any bin (TW: the deal does not move fpk, so
+                // the peak sum is computed again from the lane's two amplitudes, as fx_twin_setup did; a lane
+                // without a second ray adds exp2(kNoTwin) = 0)
+                const float pkn = TW ? fast_exp2(d.al) + fast_exp2(d.al2) : fpk;
+                fxs = act ? pkn : 0.f;
             }
             if (!FX) {
                 const int key = QUAD ? (d.pos / VW) : d.pos;
@@ -988,7 +1015,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
     }
 #ifdef NLOSGR_FXCOUNT
     if (lane == 0)
-        for (int c = 0; c < 5; ++c) atomicAdd(&g_fdbg[c], fdbg[c]);
+        for (int c = 0; c < 9; ++c) atomicAdd(&g_fdbg[c], fdbg[c]);
 #endif
     if (TW && lane == 0) {   // twins formed / split (nlosgr_fx_info)
         if (ntwin) atomicAdd(k.fx_info + 5, (int)ntwin);
@@ -1423,9 +1450,9 @@ int volume_fwd(const KArgs& ka, hipStream_t s) {
 }  // namespace nlosgr
 
 #ifdef NLOSGR_FXCOUNT
-extern "C" __attribute__((visibility("default"))) int nlosgr_debug_fx_counts(unsigned long long* out8) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_fdbg), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+extern "C" __attribute__((visibility("default"))) int nlosgr_debug_fx_counts(unsigned long long* out12) {
+    if (hipMemcpyFromSymbol(out12, HIP_SYMBOL(g_fdbg), 12 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    const unsigned long long zero[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     return hipMemcpyToSymbol(HIP_SYMBOL(g_fdbg), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
 }
 #endif

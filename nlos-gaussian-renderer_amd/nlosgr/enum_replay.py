@@ -32,9 +32,12 @@ def gaussian_frames(mu, log_scaling, rotation, mod=1.0):
     return A, s.max(1)
 
 
-def wall_point_cells(geo, p, mu, A, smax, cutoff):
+def wall_point_cells(geo, p, mu, A, smax, cutoff, details=False):
     """One wall point against every Gaussian.  Returns (box [n, 4] = i0, i1, j0, j1 inclusive, ok [n, nt, np] =
-    the cell is inside the box, passes the quadric test and has bins, kl, kh [n, nt, np])."""
+    the cell is inside the box, passes the quadric test and has bins, kl, kh [n, nt, np]).  details: a fifth
+    value, a dict of [n, nt, np] arrays for scripts/refill_replay.py: "pass" = inside the box and passing the
+    quadric test (what the enumeration queues, bins or not), "a" = |A d|^2, "ks" = the closest-approach bin,
+    "m2" = the squared Mahalanobis distance at the closest approach, and "dr" = the bin width."""
     f = lambda t: t.detach().cpu().numpy().astype(np.float64)
     st, ct = f(geo.sin_theta[p]), f(geo.cos_theta[p])
     cp, sp = f(geo.cos_phi[p]), f(geo.sin_phi[p])
@@ -86,6 +89,9 @@ def wall_point_cells(geo, p, mu, A, smax, cutoff):
     inbox = ((ii >= box[:, 0, None, None]) & (ii <= box[:, 1, None, None]) &
              (jj >= box[:, 2, None, None]) & (jj <= box[:, 3, None, None]))
     ok = inbox & (m2 <= mc2) & (kl <= kh)
+    if details:
+        return box, ok, kl.astype(np.int64), kh.astype(np.int64), {"pass": inbox & (m2 <= mc2), "a": av, "ks": ks,
+                                                                   "m2": m2, "dr": dr}
     return box, ok, kl.astype(np.int64), kh.astype(np.int64)
 
 
