@@ -1037,6 +1037,75 @@ NLOSGR_API int nlosgr_lct_store_volume(const float* field /* [2H][2W][2nv][2] */
                     const int32_t* start /* [nr + 1] */, const float* weight /* [nnz] */, int32_t nnz,
                     float* volume /* [W][nr][H] */, void* hip_stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Primal-dual passes (an addition to ABI 13: five new symbols, nothing existing changes).  The three passes of one
+ * Chambolle-Pock iteration (theta = 1) that are not an application of the operator, for
+ *
+ *     minimise over v (>= 0 with nonneg)   F(A v) + tv sum_voxels |a o grad v|_2 + l1 sum |v|
+ *
+ * on a volume [W][nr][H], axes (n, j, m), with rows [H W][nr]; A and A^T are the caller's (the LCT operator pair
+ * above).  With x the iterate, xbar the extrapolated point, q [H W][nr] the row dual and p [3][W][nr][H] the TV dual
+ * (component 0: n, 1: j, 2: m), one iteration is
+ *
+ *     z = A xbar;   q <- prox_{sigma F*}(q + sigma z)                       nlosgr_prox_rows
+ *                   p <- project_{|p|_2 <= tv}(p + sigma a o grad xbar)     nlosgr_tv_dual
+ *     g = A^T q;    u = x - tau (g + (a o grad)^T p)
+ *                   x+ = max(u - tau l1, 0) (nonneg), sign(u) max(|u| - tau l1, 0) (otherwise)
+ *                   xbar <- 2 x+ - x;  x <- x+                              nlosgr_tv_primal
+ *
+ * Gradient.  Forward differences in index units, axis k scaled by a_k >= 0 (a_n, a_j, a_m), 0 at the last index of
+ * an axis (Neumann; an axis of extent 1 contributes nothing):
+ *     (a o grad v)_k[i] = a_k (v[i + e_k] - v[i])  where i_k < N_k - 1, else 0        fp32: one subtraction, one product
+ * and its exact transpose, which never reads p_k at the last index of axis k:
+ *     t_k[i] = a_k ( (i_k > 0 ? p_k[i - e_k] : 0) - (i_k < N_k - 1 ? p_k[i] : 0) )    fp32: one subtraction, one product
+ *     ((a o grad)^T p)[i] = (t_n + t_j) + t_m                                          in this order
+ * Dual pass, per voxel, one fp32 operation each and no contraction beyond the fma written:
+ *     u_k = fma(sigma, (a o grad xbar)_k, p_k);   n = sqrtf(fma(u_2, u_2, fma(u_1, u_1, u_0 u_0)))
+ *     p = u where n <= tv, else p_k = u_k (tv / n) with one IEEE division; tv = 0 writes zeros; tv = +inf never
+ *     projects (with p = 0 and sigma = 1 the pass is then the plain gradient).
+ * Primal pass, per voxel:
+ *     w = g + ((t_n + t_j) + t_m);  u = fma(-tau, w, x);  c = tau l1 (one fp32 product, formed once)
+ *     x+ = max(u - c, 0) with nonneg, copysign(max(|u| - c, 0), u) otherwise;  xbar = fma(2, x+, -x);  x = x+
+ * Rows pass, per element, u = fma(sigma, z, q), with h the target rows and e an optional exposure table [nr], finite
+ * and >= 0 (NULL: every entry 1), d = e_j:
+ *     NLOSGR_LOSS_MSE      F(z) = 1/2 sum (z - h)^2;  q = fma(-sigma, h, u) / (1 + sigma)  (1 + sigma formed once in
+ *                          fp32).  The exposure must be NULL; gt_times and rate_floor are ignored.
+ *     NLOSGR_LOSS_POISSON  y' = max(gt_times h, 0) + eps and rho = d z + eps, eps = rate_floor > 0: the y', rho and
+ *                          eps of nlosgr_loss_irf;  F(z) = sum [rho - y' + y' log(y'/rho)], half its deviance.
+ *                          d = 0, or d so small that d d is 0 in fp32 (d < 2^-75, about 2.6e-23):  q = 0.
+ *                          A non-zero d must keep s and 4 sp y' below 2^63 in magnitude (about d >= 1e-9 sqrt(sigma y'));
+ *                          below that the squares overflow and q is not meaningful (it may be NaN).  Otherwise
+ *                            sp = sigma / (d d) (d d formed once);  s = fma(sp, eps, u / d);  A = s - 1;  c = (4 sp) y';
+ *                            D = sqrtf(fma(A, A, c));  den = (2 + A) + D where A > 0, else 2 + c / (D - A);
+ *                            q = d ( 2 fma(-sp, y', s) / den )
+ *                          This is q = d 2 (s - sp y') / (1 + s + D), the cancellation-free form of d (1 + s - D) / 2.
+ *                          Its denominator 1 + s + D = 2 + A + D is >= 2, but for A <= 0 the sum A + D is itself a
+ *                          difference that loses ulp(|s|) / 2 of q in fp32 (every digit from s = -2^25 on); there it
+ *                          is formed as c / (D - A), a sum of non-negative terms.  q < d, so nothing is clamped.
+ * Objective.  Each dual pass emits its term at the point the operator was applied to, formed in double from the fp32
+ * inputs: the rows pass F(z) (Poisson: with rho = max(d z, 0) + eps, as y' (t - log1p(t)), t = (rho - y') / y'), the
+ * dual pass sum sqrt(fma(g_m, g_m, fma(g_j, g_j, g_n g_n))) of the double gradient of xbar and sum |xbar|.  Each
+ * workgroup writes its own partial(s) in double: partials [nlosgr_prox_rows_partials] for the rows pass,
+ * [nlosgr_tv_dual_partials] = [workgroups][2] (TV, L1) for the dual pass; the caller adds them in a fixed order.
+ * One launch per pass, everything in place, one writer per element, no atomics: bitwise repeatable.
+ * Validated on the host before any launch (NLOSGR_E_INVALID): extents in 1..1024; sigma and tau finite and > 0;
+ * tv >= 0 or +inf; l1 and the axis weights finite and >= 0; rate_floor finite and > 0 (Poisson); an unknown kind; an
+ * exposure with the MSE; null pointers; and the aliasing the in-place scheme forbids (x with xbar, xbar with p, g with
+ * x or xbar, p with x, z, h or the exposure table with q, the partials with any array of their pass).  The size queries return 0 for extents out of range.
+ * ------------------------------------------------------------------------------------- */
+NLOSGR_API size_t nlosgr_prox_rows_partials(int32_t H, int32_t W, int32_t nr);
+NLOSGR_API int nlosgr_prox_rows(const float* z /* [H W][nr] */, const float* h /* [H W][nr] */,
+                    const float* exposure /* [nr] or NULL */, int32_t H, int32_t W, int32_t nr,
+                    int32_t kind /* NLOSGR_LOSS_* */, float gt_times, float rate_floor, float sigma,
+                    float* q /* [H W][nr], in place */, double* partials, void* hip_stream);
+NLOSGR_API size_t nlosgr_tv_dual_partials(int32_t W, int32_t nr, int32_t H);
+NLOSGR_API int nlosgr_tv_dual(const float* xbar /* [W][nr][H] */, int32_t W, int32_t nr, int32_t H, float a_n, float a_j,
+                    float a_m, float sigma, float tv, float* p /* [3][W][nr][H], in place */, double* partials,
+                    void* hip_stream);
+NLOSGR_API int nlosgr_tv_primal(const float* g /* [W][nr][H] */, const float* p /* [3][W][nr][H] */, int32_t W,
+                    int32_t nr, int32_t H, float a_n, float a_j, float a_m, float tau, float l1, int32_t nonneg,
+                    float* x /* [W][nr][H], in place */, float* xbar /* [W][nr][H], written */, void* hip_stream);
+
 NLOSGR_API const char* nlosgr_last_error(void);
 NLOSGR_API int nlosgr_abi_version(void);
 

@@ -21,7 +21,10 @@ Layers:
                            passes around torch.fft, rsd_capture; confocal or one laser spot
     nlosgr.lct             light-cone transform of a confocal capture (Wiener-filtered inversion): four HIP passes
                            around torch.fft, lct_capture; LctOperator, the confocal forward operator and its adjoint
-                           at FFT speed, lct_solve (Landweber, FISTA), lct_solve_capture
+                           at FFT speed, lct_solve (Landweber, FISTA), lct_solve_pd (TV, sparsity, a Poisson data
+                           term), lct_solve_capture
+    nlosgr.prox            the primal-dual solver behind lct_solve_pd: three HIP passes (the row prox, the TV dual
+                           and primal updates) and the loop over two operator callables, primal_dual
     nlosgr.lattice         the wall's lattice that fk, rsd and lct share: wall_lattice, the row lookup, the capture
                            prologue and crop
     nlosgr.forward_project its adjoint: voxel grid -> transients, voxel_transient, operator_norm, landweber
@@ -40,14 +43,17 @@ __all__ = ["Geometry", "build_geometry", "relay_wall_grid", "volume_box_point", 
            "backproject_capture", "time_filter", "phasor_capture", "phasor_kernel",
            "fk_capture", "fk_migrate", "rsd_capture", "rsd_reconstruct", "lct_capture", "lct_reconstruct",
            "LctOperator", "lct_project", "lct_adjoint", "lct_solve", "lct_solve_capture", "lct_load_volume",
-           "lct_store_rows", "lct_load_rows", "lct_store_volume"]
+           "lct_store_rows", "lct_load_rows", "lct_store_volume", "lct_solve_pd",
+           "primal_dual", "prox_rows", "tv_dual_step", "tv_primal_step", "tv_gradient", "tv_divergence"]
 
 _BP_NAMES = ("backproject_capture", "time_filter")
 _PH_NAMES = ("phasor_capture", "phasor_kernel")
 _FK_NAMES = ("fk_capture", "fk_migrate")
 _RSD_NAMES = ("rsd_capture", "rsd_reconstruct")
 _LCT_NAMES = ("lct_capture", "lct_reconstruct", "LctOperator", "lct_project", "lct_adjoint", "lct_solve",
-              "lct_solve_capture", "lct_load_volume", "lct_store_rows", "lct_load_rows", "lct_store_volume")
+              "lct_solve_capture", "lct_load_volume", "lct_store_rows", "lct_load_rows", "lct_store_volume",
+              "lct_solve_pd")
+_PROX_NAMES = ("primal_dual", "prox_rows", "tv_dual_step", "tv_primal_step", "tv_gradient", "tv_divergence")
 _MESH_NAMES = ("Mesh", "isosurface", "extract_mesh", "write_ply", "read_ply")
 
 
@@ -73,4 +79,7 @@ def __getattr__(name):
     if name in _LCT_NAMES:
         from . import lct
         return getattr(lct, name)
+    if name in _PROX_NAMES:
+        from . import prox
+        return getattr(prox, name)
     raise AttributeError(f"module 'nlosgr' has no attribute {name!r}")

@@ -124,6 +124,8 @@ EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "
            "nlosgr_rsd_load", "nlosgr_rsd_kernel", "nlosgr_rsd_apply", "nlosgr_rsd_gather",
            "nlosgr_lct_load", "nlosgr_lct_kernel", "nlosgr_lct_filter", "nlosgr_lct_store",
            "nlosgr_lct_load_volume", "nlosgr_lct_store_rows", "nlosgr_lct_load_rows", "nlosgr_lct_store_volume",
+           "nlosgr_prox_rows_partials", "nlosgr_prox_rows", "nlosgr_tv_dual_partials", "nlosgr_tv_dual",
+           "nlosgr_tv_primal",
            "nlosgr_set_batch_budgets", "nlosgr_get_batch_budgets", "nlosgr_last_error", "nlosgr_abi_version"]
 
 _lib = None
@@ -263,6 +265,16 @@ def load():
     lib.nlosgr_lct_load_rows.restype = ctypes.c_int
     lib.nlosgr_lct_store_volume.argtypes = lib.nlosgr_lct_store.argtypes
     lib.nlosgr_lct_store_volume.restype = ctypes.c_int
+    lib.nlosgr_prox_rows_partials.argtypes = [I32, I32, I32]
+    lib.nlosgr_prox_rows_partials.restype = ctypes.c_size_t
+    lib.nlosgr_prox_rows.argtypes = [_P, _P, _P, I32, I32, I32, I32, F32, F32, F32, _P, _P, _P]
+    lib.nlosgr_prox_rows.restype = ctypes.c_int
+    lib.nlosgr_tv_dual_partials.argtypes = [I32, I32, I32]
+    lib.nlosgr_tv_dual_partials.restype = ctypes.c_size_t
+    lib.nlosgr_tv_dual.argtypes = [_P, I32, I32, I32, F32, F32, F32, F32, F32, _P, _P, _P]
+    lib.nlosgr_tv_dual.restype = ctypes.c_int
+    lib.nlosgr_tv_primal.argtypes = [_P, _P, I32, I32, I32, F32, F32, F32, F32, F32, I32, _P, _P, _P]
+    lib.nlosgr_tv_primal.restype = ctypes.c_int
     lib.nlosgr_bboxes.argtypes = [PG, ctypes.c_float, _P, _P]
     lib.nlosgr_bboxes.restype = ctypes.c_int
     lib.nlosgr_set_batch_budgets.argtypes = [ctypes.c_double, ctypes.c_double]

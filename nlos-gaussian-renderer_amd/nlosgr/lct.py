@@ -36,13 +36,15 @@ its exact adjoint (LctOperator; include/nlosgr.h, "LCT operator pair"):
 with w_j = (r0 + j dr)^power, power -4..4, and nothing clamped, so both take a residual.  LctOperator.project is
 differentiable (its backward is the adjoint); lct_solve runs projected Landweber or FISTA steps on 1/2 |A v - h|^2 at
 FFT speed on the capture's full lattice, lct_solve_capture does so for a loaded capture, and
-voxel_fit.VoxelFitStep(operator=) fits Gaussians through it.  Not built: regularisers (TV, sparsity), a Poisson data
-term in lct_solve, the non-confocal case.
+voxel_fit.VoxelFitStep(operator=) fits Gaussians through it.  lct_solve_pd adds what a real capture needs: total
+variation, sparsity and a Poisson data term with the falloff as a per-bin exposure, by a primal-dual iteration
+(nlosgr.prox: three more HIP passes around the same operator pair).  Not built: the non-confocal case.
 
 No CPU fallback.
 
     python -m nlosgr.lct CAPTURE.mat --start S --end E [--power P] [--snr X] [--nv N] [--backprop] --out lct.npz
-        [--mesh lct.ply --level-frac F] [--iterations N [--no-accelerate] [--falloff Q]]
+        [--mesh lct.ply --level-frac F] [--iterations N [--no-accelerate] [--falloff Q]
+        [--tv T] [--l1 L] [--loss mse|poisson] [--rate-floor E] [--gt-times G]]
 """
 import functools
 
@@ -54,6 +56,10 @@ from .lattice import _extents, _f32, _gpu, _work, capture_result, confocal_latti
 
 MAX_CELLS = 2048
 MODE_WIENER, MODE_BACKPROP, MODE_GIVEN = 0, 1, 2
+# LctOperator.norm() is a power iteration: it approaches |A|^2 from below, and the primal-dual steps need a bound from
+# above.  The float64 power iteration run to convergence (1e-12) on the test lattices is at most 1.000136 times its
+# 8-iteration estimate (the windows that start at bin 35; 1.00002 or less on the others): rounded up to 1.01.
+NORM_SAFETY = 1.01
 
 
 def _cells(nv, nr):
@@ -518,6 +524,33 @@ def lct_solve(rows, op, iterations=30, nonneg=True, step=None, x0=None, accelera
 
 
 @torch.no_grad()
+def lct_solve_pd(rows, op, iterations=100, tv=0.0, l1=0.0, loss="mse", exposure=None, gt_times=1.0, rate_floor=1.0,
+                 weights=(1.0, 1.0, 1.0), nonneg=True, norm=None, tau=None, sigma=None, x0=None):
+    """(volume [W, nr, H], objective [iterations], terms [iterations, 3]): prox.primal_dual with A = op (an
+    LctOperator), for  F(A v) + tv sum |a o grad v|_2 + l1 sum |v|  over v >= 0 (any v without nonneg).  loss "mse":
+    F = 1/2 |A v - rows|^2.  loss "poisson": the rows are photon counts, F = sum [rho - y' + y' log(y'/rho)] with
+    y' = max(gt_times rows, 0) + rate_floor and rho = exposure_j (A v) + rate_floor; exposure fp32 [nr] >= 0 (None:
+    ones) is where a capture's falloff belongs.  tv, l1 are absolute here (lct_solve_capture scales them); weights:
+    the gradient's axis weights (n, j, m).
+    norm: an upper bound of |A|^2; by default NORM_SAFETY op.norm(): the power iteration bounds |A|^2 from below, and
+    in float64, run to convergence on the test lattices, it ends at most 1.000136 times its 8-iteration estimate,
+    which NORM_SAFETY = 1.01 rounds up.  tau, sigma: the steps, 1 / sqrt(norm + 4 sum a^2) by default (the second part
+    with tv > 0 only).  objective and terms as prox.primal_dual's: float64 on the device, at the point the operator is
+    applied to, before the update; no host read inside the loop."""
+    from . import prox
+    if not isinstance(op, LctOperator):
+        raise TypeError("nlosgr: lct_solve_pd takes an LctOperator")
+    rows = _gpu(rows, torch.float32, "lct_solve_pd")
+    if tuple(rows.shape) != op.rows_shape or rows.device != op.device:
+        raise ValueError(f"nlosgr: the rows must be float32 {op.rows_shape} on {op.device}")
+    norm = NORM_SAFETY * op.norm() if norm is None else float(norm)
+    z = torch.empty_like(rows)
+    return prox.primal_dual(rows, lambda v: op.forward(v, out=z), op.adjoint, op.volume_shape, norm, iterations, tv=tv,
+                            l1=l1, loss=loss, exposure=exposure, gt_times=gt_times, rate_floor=rate_floor,
+                            weights=weights, nonneg=nonneg, tau=tau, sigma=sigma, x0=x0)
+
+
+@torch.no_grad()
 def lct_reconstruct(rows, H, W, sx, sz, r0, dr, power=4, snr=0.8, nv=None, backprop=False, perm=None, x_along="n",
                     inverse=None):
     """[W, nr, H] fp32: the light-cone transform of rows [H W, nr], the lattice, perm, x_along, r0, dr and power as
@@ -559,7 +592,7 @@ def lct_capture(data_kwargs, start, end, power=4, snr=0.8, nv=None, backprop=Fal
 
 @torch.no_grad()
 def lct_solve_capture(data_kwargs, start, end, falloff=3, power=0, iterations=30, accelerate=True, nv=None,
-                      crop=True):
+                      crop=True, tv=0.0, l1=0.0, loss="mse", rate_floor=1.0, gt_times=1.0, weights=(1.0, 1.0, 1.0)):
     """The non-negative least-squares volume of a confocal capture on its own lattice: lct_solve with
     LctOperator(power=power) on the rows of bins [floor(start), floor(start) + end - start), bin j multiplied by
     (r0 + j dr)^falloff first, as voxel_fit.fit_capture does.  Returns the keys of lct_capture plus "objective"
@@ -568,17 +601,46 @@ def lct_solve_capture(data_kwargs, start, end, falloff=3, power=0, iterations=30
     Why falloff=3 with power=0 is the default, not power=-3 on the raw rows: both state the same physical model
     (A at power -3 is the confocal transient), but at power -3 the operator carries r^-3 itself, and in a window
     that starts at r0 = 0 its first bins give it a norm of about 1e11: the step 1 / norm is then so small that the
-    far voxels do not move and the solve stalls.  Moving the r^3 to the rows leaves an operator of norm about 1."""
+    far voxels do not move and the solve stalls.  Moving the r^3 to the rows leaves an operator of norm about 1.
+
+    With tv > 0, l1 > 0 or loss="poisson" the volume is lct_solve_pd's instead (accelerate is then unused), and the
+    result also holds "terms" [iterations, 3] and "lambda0" (a float).  tv and l1 are fractions of
+    lambda0 = max(-A^T grad F(0)), the l1 above which the zero volume is the minimiser: max A^T h for the MSE,
+    max A^T (e (y'/eps - 1)) for the Poisson term; one adjoint, so the capture's scale need not be known.
+    A lambda0 that comes out negative (rows with nothing above zero) is taken as 0, and tv and l1 with it.
+    loss="poisson": multiplying counts by r^falloff would break their statistics, so the rows stay raw (times
+    gt_times inside the likelihood) and the falloff becomes the exposure e_j = r_j^-falloff (0 where r_j <= 0,
+    built in float64); eps = rate_floor.  weights: lct_solve_pd's."""
+    from . import prox
+    kind = prox._loss(loss)
     c = confocal_lattice(data_kwargs, start, end, "the LCT solver")
     rows = _gpu(c.rows.float(), torch.float32, "lct_solve_capture")
-    if falloff:
-        radii = c.r0 + c.dr * torch.arange(c.nr, dtype=torch.float64, device=rows.device)
+    radii = c.r0 + c.dr * torch.arange(c.nr, dtype=torch.float64, device=rows.device)
+    exposure = None
+    if kind == _lib.LOSS_POISSON:
+        exposure = torch.where(radii > 0, radii.clamp(min=1e-300).pow(-float(falloff)), torch.zeros_like(radii)).float()
+    elif falloff:
         rows = (rows.double() * radii.pow(float(falloff))[None]).float()
     op = LctOperator(c.H, c.W, c.sx, c.sz, c.r0, c.dr, c.nr, power=power, nv=nv, perm=c.perm, x_along=c.x_along,
                      device=rows.device)
-    vol, objective = lct_solve(rows, op, iterations=iterations, accelerate=accelerate)
+    more = {}
+    if float(tv) == 0 and float(l1) == 0 and kind == _lib.LOSS_MSE:
+        vol, objective = lct_solve(rows, op, iterations=iterations, accelerate=accelerate)
+    else:
+        if kind == _lib.LOSS_POISSON:
+            if not (float(rate_floor) > 0 and np.isfinite(float(rate_floor))):
+                raise ValueError("nlosgr: rate_floor must be finite and > 0")
+            pull = (rows.double().mul(float(gt_times)).clamp_(min=0.0) * (exposure.double() / float(rate_floor))[None]).float()
+        else:
+            pull = rows
+        lambda0 = max(float(op.adjoint(pull).max()), 0.0)          # rows that pull no voxel up: no weight at all
+        vol, objective, terms = lct_solve_pd(rows, op, iterations=iterations, tv=float(tv) * lambda0,
+                                             l1=float(l1) * lambda0, loss=loss, exposure=exposure, gt_times=gt_times,
+                                             rate_floor=rate_floor, weights=weights)
+        more = {"terms": terms, "lambda0": lambda0}
     out = capture_result(data_kwargs, op.grid(c.xs, c.zs, c.y0), vol, crop)
     out["objective"] = objective
+    out.update(more)
     return out
 
 
@@ -597,6 +659,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-accelerate", dest="accelerate", action="store_false",
                     help="with --iterations: plain Landweber steps instead of FISTA")
     ap.add_argument("--falloff", type=float, default=3.0, help="with --iterations: multiply bin j by (r0 + j dr)^falloff")
+    ap.add_argument("--tv", type=float, default=0.0,
+                    help="with --iterations: total-variation weight as a fraction of lambda0 (lct_solve_capture); with "
+                         "--tv, --l1 or --loss poisson the primal-dual solver runs instead of FISTA")
+    ap.add_argument("--l1", type=float, default=0.0, help="with --iterations: sparsity weight as a fraction of lambda0")
+    ap.add_argument("--loss", choices=("mse", "poisson"), default="mse",
+                    help="with --iterations: the data term; poisson takes the raw counts and --falloff as an exposure")
+    ap.add_argument("--rate-floor", type=float, default=1.0, help="with --loss poisson: the rate floor eps, in counts")
+    ap.add_argument("--gt-times", type=float, default=1.0, help="with --loss poisson: the factor that brings the rows to counts")
     a = _cli.parse(ap, argv)
     if a.iterations < 0:
         ap.error("--iterations must be >= 0")
@@ -608,6 +678,15 @@ def parse_args(argv=None):
         ap.error("--snr must be greater than 0")
     if a.nv is not None and not 1 <= a.nv <= MAX_CELLS:
         ap.error(f"--nv must be in 1..{MAX_CELLS}")
+    if not (0 <= a.tv < float("inf") and 0 <= a.l1 < float("inf")):
+        ap.error("--tv and --l1 must be finite and >= 0")
+    if not 0 < a.rate_floor < float("inf"):
+        ap.error("--rate-floor must be finite and greater than 0")
+    if not abs(a.gt_times) < float("inf"):
+        ap.error("--gt-times must be finite")
+    a.primal_dual = a.tv > 0 or a.l1 > 0 or a.loss != "mse"
+    if a.primal_dual and not a.iterations:
+        ap.error("--tv, --l1 and --loss poisson belong to --iterations")
     return a
 
 
@@ -616,9 +695,13 @@ def main(argv=None):
     dk = _cli.open_capture(a.capture, "the light-cone transform")
     if a.iterations:
         out = lct_solve_capture(dk, a.start, a.end, falloff=a.falloff, power=a.power, iterations=a.iterations,
-                                accelerate=a.accelerate, nv=a.nv)
+                                accelerate=a.accelerate, nv=a.nv, tv=a.tv, l1=a.l1, loss=a.loss,
+                                rate_floor=a.rate_floor, gt_times=a.gt_times)
         extra = {"objective": out["objective"].cpu().numpy()}
         how = f"{a.iterations} {'FISTA' if a.accelerate else 'Landweber'} steps, falloff {a.falloff:g}"
+        if a.primal_dual:
+            extra.update(terms=out["terms"].cpu().numpy(), lambda0=np.float64(out["lambda0"]))
+            how = f"{a.iterations} primal-dual steps, {a.loss}, tv {a.tv:g}, l1 {a.l1:g}, falloff {a.falloff:g}"
     else:
         out = lct_capture(dk, a.start, a.end, power=a.power, snr=a.snr, nv=a.nv, backprop=a.backprop)
         extra = {}
