@@ -179,6 +179,13 @@ typedef struct {
                                             drain) instead of two adjacent rays of a pair per lane (A/B, tests) */
 #define NLOSGR_FLAG_FX_TWIN_STATS 0x20000 /* forward twin drain: also record the longest twin (bins) in
                                              nlosgr_fx_info (one global atomic per twin: diagnostics, slow) */
+#define NLOSGR_FLAG_FX_TRIM      0x40000 /* forward no-occlusion FX drain: each (wall point, Gaussian) pair's support
+                                            ends where its value falls under a quarter of the drain's unit 2^-E,
+                                            when that is inside the cutoff; a pair that peaks below a quarter unit is
+                                            skipped.  Such terms round to zero units in that drain anyway, so the
+                                            histogram keeps its per-term rounding bound; rays are paired differently,
+                                            so it is not bitwise the untrimmed one.  Other forwards and the backward
+                                            ignore it */
 
 /* Scratch bytes needed by fwd/bwd for this problem (caller allocates, 256-B aligned); includes
  * nwall*ng*24 B for the ray cache when opt->ray_cache is set (OCCL mode: the row cache,

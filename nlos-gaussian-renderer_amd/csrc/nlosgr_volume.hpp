@@ -125,10 +125,33 @@ __device__ __forceinline__ void load_rec(const GaussRec& r, Pair& P, float mu[3]
     P.N[2] = r.e.x; P.N[3] = r.e.y; P.N[4] = r.e.z; P.N[5] = r.e.w;
 }
 
-// f: the Gaussian's feature row (k_feat floats; registers or global)
-template <int PRESET, bool DENSE>
+// Trimmed support of the no-occlusion FX forward (NLOSGR_FLAG_FX_TRIM).  That drain rounds every term to the
+// nearest unit 2^-E, and its twin lanes round the SUM of two rays' terms, so a term below a quarter unit adds
+// exactly 0.  With lw = log2(w 2^E) the value at Mahalanobis distance m is 2^(lw + log2 sin(theta) - m^2 log2(e) / 2)
+// <= 2^(lw - m^2 log2(e) / 2) (sin(theta) <= 1 is ignored), which is below 2^-(2 + kTrimMargin) units for
+// m^2 > 2 ln 2 (lw + 2 + kTrimMargin): the pair's support radius is the smaller of that and the cutoff.
+// kTrimMargin widens the radius by what the kernel's own value of a dropped term can exceed the exact one,
+// in log2: the recurrence's drift within a round, <= kStepsTwin ulp = 36 x 1.2e-7 relative (kRecurrence), 6.2e-6;
+// v_log_f32 and v_exp_f32, 1 ulp each, 3.8e-6 of an |lw| <= 32 and 1.7e-7; about ten fp32 roundings of exponent
+// terms below 64 (half an ulp each, 3.8e-6), 4e-5; v_rcp / v_sqrt in the half width hk (2 ulp of hk^2, times
+// |ga| hk^2 <= m_c^2 log2(e) / 2 = 23.4), 1.1e-5; and the rounding of ks - hk before ceil / floor pick the end
+// bins, which moves the edge by up to ulp(ks) / 2 = 2.4e-4 bins at ks < 4096 (validate: nr <= 4096), 2 |ga| hk
+// = 46.9 / hk per bin of it, 1.14e-2 for a ray at least one bin wide each side.  Sum 1.15e-2 < 2^-6.  (A ray
+// narrower than a bin whose edge lies within ulp(ks) of a bin centre is decided either way by that rounding,
+// as it is at the cutoff itself.)  Every decision with the margin is conservative: it only keeps more.
+constexpr float kTrimMargin = 0.015625f;             // 2^-6, log2
+constexpr float kTrim = 1.38629436111989062f;        // 2 ln 2
+constexpr float kTrimQuarter = 2.0f + kTrimMargin;   // a pair with lw + kTrimQuarter <= 0 peaks below a quarter unit
+__device__ __forceinline__ float fx_trim_m2(float lw, float mc2) {
+    return fminf(mc2, kTrim * (lw + kTrimQuarter));   // (add and multiply by literals: no constant held in a VGPR)
+}
+
+// f: the Gaussian's feature row (k_feat floats; registers or global).  TRIM (the no-occlusion FX forward) with
+// trim set: the quadric and the box take the pair's trimmed radius (fx_trim_m2 of log2(w) + fxE) for the cutoff
+template <int PRESET, bool DENSE, bool TRIM = false>
 __device__ __forceinline__ void pair_setup(const KArgs& k, const float* f, const float mu[3], float px, float py,
-                                           float pz, const float* lin, float mc2, Pair& P) {
+                                           float pz, const float* lin, float mc2, Pair& P, float fxE = 0.f,
+                                           bool trim = false) {
     P.q[0] = px - mu[0]; P.q[1] = py - mu[1]; P.q[2] = pz - mu[2];
     for (int r = 0; r < 3; ++r) P.u0[r] = P.A[3 * r] * P.q[0] + P.A[3 * r + 1] * P.q[1] + P.A[3 * r + 2] * P.q[2];
     view_dir<PRESET>(-P.q[0], -P.q[1], -P.q[2], P.dir[0], P.dir[1], P.dir[2], P.nrm);
@@ -143,7 +166,12 @@ __device__ __forceinline__ void pair_setup(const KArgs& k, const float* f, const
     const float wv0 = P.A[0] * P.u0[0] + P.A[3] * P.u0[1] + P.A[6] * P.u0[2];
     const float wv1 = P.A[1] * P.u0[0] + P.A[4] * P.u0[1] + P.A[7] * P.u0[2];
     const float wv2 = P.A[2] * P.u0[0] + P.A[5] * P.u0[1] + P.A[8] * P.u0[2];
-    const float kap = P.u0[0] * P.u0[0] + P.u0[1] * P.u0[1] + P.u0[2] * P.u0[2] - mc2;
+    float mp2 = mc2, mcut = k.opt.cutoff;
+    if (TRIM && trim) {   // (w <= 0 or NaN: the caller skips such a pair whatever its radius)
+        mp2 = fmaxf(fx_trim_m2(flog2(P.w) + fxE, mc2), 0.f);
+        mcut = fsqrt(mp2);
+    }
+    const float kap = P.u0[0] * P.u0[0] + P.u0[1] * P.u0[1] + P.u0[2] * P.u0[2] - mp2;
     P.M[0] = wv0 * wv0 - kap * P.N[0];
     P.M[1] = 2.0f * (wv0 * wv1 - kap * P.N[1]);
     P.M[2] = 2.0f * (wv0 * wv2 - kap * P.N[2]);
@@ -151,7 +179,7 @@ __device__ __forceinline__ void pair_setup(const KArgs& k, const float* f, const
     P.M[4] = 2.0f * (wv1 * wv2 - kap * P.N[4]);
     P.M[5] = wv2 * wv2 - kap * P.N[5];
     // bounding-sphere cone -> (theta, phi) index box (angles via one fast atan2, widened by a margin)
-    const float Rb = k.opt.cutoff * P.smax * 1.0001f + 1e-7f;
+    const float Rb = mcut * P.smax * 1.0001f + 1e-7f;
     const float dx = -P.q[0], dy = -P.q[1], dz = -P.q[2];
     const float rxy2 = dx * dx + dy * dy;
     const float dist2 = rxy2 + dz * dz;

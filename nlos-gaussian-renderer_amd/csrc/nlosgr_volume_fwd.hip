@@ -627,6 +627,9 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
     float* rout = RAYS ? k.ray_out + (size_t)p * nt * np_ * nr : nullptr;
     const float rscale = k.opt.ray_scale;
     const int flags = k.opt.flags;
+    // the trimmed support (fx_trim_m2, nlosgr_volume.hpp): the no-occlusion FX drains, twin, one ray and bright
+    constexpr bool TRIMK = FX && MODE == NLOSGR_MODE_NOOCL && !CACHE;
+    const bool trim = TRIMK && (flags & NLOSGR_FLAG_FX_TRIM) != 0;   // launch-uniform
     // FX: log2 of the unit scale, folded into every pair's log2 amplitude; per-lane peak bookkeeping
     const float fxE = FX ? (float)k.fx_info[0] : 0.f;
     const float fxS = FX ? fast_exp2(fxE) : 1.f;   // exact: fxE is an integer
@@ -644,9 +647,10 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
     unsigned long long nsamp = 0;
 
 #ifdef NLOSGR_FXCOUNT
-    unsigned long long fdbg[9] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};   // wave-uniform diagnostics
+    unsigned long long fdbg[11] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};   // wave-uniform diagnostics
     // ([0..4]: the rounds' bank-pair occupancy; [5..8]: refills, entries taken, refills taking < 32 entries,
-    // refills after the chunk's enumeration ended)
+    // refills after the chunk's enumeration ended; [9]: rays taken with bins (a twin counts two); [10]: pairs
+    // dropped by NLOSGR_FLAG_FX_TRIM because they peak below a quarter unit)
 #endif
     Drain d;
     d.pos = 0; d.rem = 0; d.t = 0.f; d.ga = 0.f; d.al = 0.f; d.st = 0.f;
@@ -684,9 +688,17 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                 float mu[3];
                 load_rec(nrec, P, mu);
                 if (BR) P.sigma = fabsf(P.sigma);
-                pair_setup<PRESET, DENSE>(k, k.g.features + (size_t)gl * k.g.k_feat, mu, px, py, pz, lin, mc2, P);
+                pair_setup<PRESET, DENSE, TRIMK>(k, k.g.features + (size_t)gl * k.g.k_feat, mu, px, py, pz, lin, mc2, P,
+                                                 fxE, trim);
                 more = (P.w > 0.f) && P.i0 <= P.i1 && P.j0 <= P.j1;
                 lw = more ? flog2(P.w) + fxE : 0.f;
+                if (trim) {   // a pair that peaks below a quarter unit adds nothing
+                    const bool dead = more && !(lw + kTrimQuarter > 0.f);
+#ifdef NLOSGR_FXCOUNT
+                    if (!BR) fdbg[10] += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(dead));
+#endif
+                    more = more && !dead;
+                }
                 sc = P.sigma * cdt;
                 wc = more ? P.w * cdt * fxS : 0.f;   // netf: the value's scale rides on T
             }
@@ -733,6 +745,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) u0[c] = __shfl(P.u0[c], slot);
                 const float lws = __shfl(lw, slot);
+                const float mc2r = trim ? fx_trim_m2(lws, mc2) : mc2;   // the ray's support radius, squared
                 const float scs = MODE == NLOSGR_MODE_NETF ? __shfl(sc, slot) : 0.f;
                 const float wcs = MODE == NLOSGR_MODE_NETF ? __shfl(wc, slot) : 0.f;
                 bool got = false;
@@ -742,7 +755,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                         const bool twin = ((e >> kGroupShift) & 3u) != 0u;
                         float pk = 0.f;
                         // (j + 1 <= j1 < np for a twin entry; a single reads its own cell twice)
-                        tcode = fx_twin_setup(A, u0, lws, tth[i], tph[j], tph[twin ? j + 1 : j], twin, nr, mc2, r0, dr,
+                        tcode = fx_twin_setup(A, u0, lws, tth[i], tph[j], tph[twin ? j + 1 : j], twin, nr, mc2r, r0, dr,
                                               inv_dr, d, pk);
                         got = tcode != 0;
                         if ((flags & NLOSGR_FLAG_FX_TWIN_STATS) && tcode == 2) atomicMax(k.fx_info + 7, d.rem);
@@ -755,7 +768,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                 } else if (take && !(flags & 1)) {
                     // dense: consecutive queue entries start 37 bins apart (distinct claim keys)
                     const int stag = dense_wrap<MODE, DENSE>() ? (int)(((unsigned)(qhead + r) * 37u) % (unsigned)nr) : 0;
-                    got = drain_setup<MODE, DENSE, RAYS>(A, u0, lws, scs, wcs, tth[i], tph[j], i, j, np_, nr, mc2,
+                    got = drain_setup<MODE, DENSE, RAYS>(A, u0, lws, scs, wcs, tth[i], tph[j], i, j, np_, nr, mc2r,
                                                          r0, dr, inv_dr, f0log2, d, stag);
                     if (got && !NLOSGR_FCOUNT_ON) nsamp += (unsigned)(d.rem + (dense_wrap<MODE, DENSE>() ? d.wrap : 0));
                     if (MODE == NLOSGR_MODE_NETF && TAIL && QUADF) d.T *= d.wc;   // the weight rides on T
@@ -768,6 +781,9 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                     }
                 }
                 nseg += NLOSGR_FCOUNT_ON ? 0u : (unsigned)__popcll(__builtin_amdgcn_ballot_w64(got));
+#ifdef NLOSGR_FXCOUNT
+                if (FX && !BR && !TW) fdbg[9] += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(got));
+#endif
                 const int ntake = min(nidle, qcount);
                 qhead = (qhead + ntake) & (kRQ - 1);
                 qcount -= ntake;
@@ -775,6 +791,9 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
                     const unsigned long long tm = __builtin_amdgcn_ballot_w64(tcode == 2);
                     const unsigned long long sm = __builtin_amdgcn_ballot_w64(tcode == 3);
                     ntwin += (unsigned)__popcll(tm);
+#ifdef NLOSGR_FXCOUNT
+                    fdbg[9] += (unsigned long long)(__popcll(__builtin_amdgcn_ballot_w64(tcode != 0)) + __popcll(tm));
+#endif
                     if (sm) {
                         // split twins: the second ray returns to the queue's tail as a single entry (the queue
                         // just gave up ntake >= popc(sm) entries, so the ring cannot overflow)
@@ -1015,7 +1034,7 @@ __device__ __forceinline__ void fwd_body(const KArgs& k) {
     }
 #ifdef NLOSGR_FXCOUNT
     if (lane == 0)
-        for (int c = 0; c < 9; ++c) atomicAdd(&g_fdbg[c], fdbg[c]);
+        for (int c = 0; c < 11; ++c) atomicAdd(&g_fdbg[c], fdbg[c]);
 #endif
     if (TW && lane == 0) {   // twins formed / split (nlosgr_fx_info)
         if (ntwin) atomicAdd(k.fx_info + 5, (int)ntwin);

@@ -107,6 +107,7 @@ FLAG_FX_MAXUNIT = 0x4000   # FX drain unit from the largest bound (round-5 rule;
 FLAG_TILE_NOBIN = 0x8000   # ray-tile engine: in-kernel cull instead of the tile bins (A/B)
 FLAG_FX_NOTWIN = 0x10000   # no-occlusion FX drain: one ray per lane instead of two adjacent rays (A/B, tests)
 FLAG_FX_TWIN_STATS = 0x20000  # twin drain: record the longest twin in fx_info (diagnostics, slow)
+FLAG_FX_TRIM = 0x40000     # no-occlusion FX drain: a pair's support ends where its value is under a quarter unit
 
 # every symbol include/nlosgr.h declares (tests check the exports against this list)
 EXPORTS = ["nlosgr_workspace_bytes", "nlosgr_render_fwd", "nlosgr_render_bwd", "nlosgr_count_support", "nlosgr_fx_info",

@@ -47,7 +47,12 @@ def wall_point_cells(geo, p, mu, A, smax, cutoff, details=False):
     nr, nt, np_ = len(r), len(st), len(cp)
     r0 = r[0]
     dr = (r[-1] - r[0]) / (nr - 1)
+    # cutoff: one number, or one radius per Gaussian [n] (scripts/trim_estimate.py: the trimmed support of
+    # NLOSGR_FLAG_FX_TRIM, which takes the pair's own radius in the box, the quadric and the bin range)
+    cutoff = np.asarray(cutoff, np.float64)
     mc2 = cutoff * cutoff
+    if mc2.ndim:
+        mc2 = mc2[:, None, None]
     n = len(mu)
     # the box (pair_setup)
     d = mu - w

@@ -507,6 +507,12 @@ class TrainStep:
         cache = use_ray_cache(cfg, self.geo, ng)
         ev = self.events
         stream = torch.cuda.current_stream(m._mu.device) if ev else None
+        # the culled no-occlusion support-selection forward ends each pair's support where its terms round to zero
+        # units of the fixed-point drain (FLAG_FX_TRIM; forwards that do not take that drain ignore the bit).  The
+        # backward keeps the full cutoff: its sums are floats
+        fcfg = cfg
+        if cfg.mode == "noocl" and cfg.selection == "support" and cfg.cutoff > 0 and not cache:
+            fcfg = replace(cfg, flags=cfg.flags | _lib.FLAG_FX_TRIM)
         if ev:
             ev["fwd"][0].record(stream)
         if self.fwd_order == "slab" and not cache and cfg.mode != "occl" and cfg.selection == "support" and ng > 64:
@@ -517,10 +523,10 @@ class TrainStep:
             # 4 / 16 / 32 slabs the same, no slabs (size only) 1077, with lateral cells 1101.  The
             # histogram is order-independent up to fp32 summation order.
             fp = slab_order(args[0], None, 8, 1, size=args[1].max(1).values, centroid=self.wall_c)
-            out = render_forward(*(tuple(t[fp].contiguous() for t in args[:5]) + (args[5],)), cfg, True, False,
+            out = render_forward(*(tuple(t[fp].contiguous() for t in args[:5]) + (args[5],)), fcfg, True, False,
                                  ray_cache=cache)
         else:
-            out = render_forward(*args, cfg, True, False, ray_cache=cache)
+            out = render_forward(*args, fcfg, True, False, ray_cache=cache)
         if ev:
             ev["fwd"][1].record(stream)
         hist, ws = out[0], (out[2] if cache else None)
